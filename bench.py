@@ -2,7 +2,14 @@
 RayTracingWeekend.cpp:211-250) on the BASELINE.json workloads.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload T|C4|C2|C3|C5|C1]
-                  [--scaling strong|weak]
+                  [--scaling strong|weak] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed step left its caller
+(rank 0's `accum` and `canvas`, see dump_outputs) as DIR/<name>.npy; the
+inputs are a function of the arguments alone (seeded scenes, per-sample RNG
+keys), so two builds can be compared output for output.  --full adds what the
+headline figure does not need: the `cpu_baseline` measurement.
 
 --gpus N > 1 runs one process per GPU: under torch.distributed.run (the
 driver's launch: RANK / WORLD_SIZE / LOCAL_RANK in the environment), or, when
@@ -27,9 +34,9 @@ ranks and rank 0's, for diagnosing an N > 1 run), `roofline` for the traversal k
 library actually launched (rtw_scene_query names it): HIP-event-timed launch
 durations; the VALU roofline (the binding resource) from the
 PMC record of that kernel, build and workload when one is committed under
-profiles/pmc/, else the §8(d) HBM figure alone; and `cpu_baseline` (the
-reference's own code, oracle/_ref/rtw_ref, on the host cores; or the C
-restatement when that binary is absent).
+profiles/pmc/, else the §8(d) HBM figure alone; and, with --full,
+`cpu_baseline` (the reference's own code, oracle/_ref/rtw_ref, on the host
+cores; or the C restatement when that binary is absent; null in a plain run).
 """
 from __future__ import annotations
 
@@ -114,10 +121,16 @@ def parse():
                          "mode, statistical parity only, reported as its own line")
     ap.add_argument("--paths", type=int, default=0, help="wavefront paths in flight (0 = library default)")
     ap.add_argument("--no-kernel-times", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-spp", type=int, default=0, help="CPU baseline sample: spp of the full image (0 = auto)")
     ap.add_argument("--ppm", default="", help="write the rank-0 canvas of the last step here")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (rank 0's accum and canvas) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     w = dict(WORKLOADS[a.workload])
     custom = False
     for k in ("scene", "nx", "ny", "spp", "depth", "bvh"):
@@ -301,6 +314,36 @@ def bounded_valu(out):
     return out
 
 
+# --dump-outputs: at most this many bytes over all the files (the limit is
+# 64 MB; the .npy headers take 128 bytes each)
+DUMP_MAX_BYTES = 60 * 1000 * 1000
+DUMP_SEED = 20240  # of the pixel sample of an output larger than its share
+
+
+def dump_outputs(directory, arrays: dict, max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """Write each array of `arrays` ({name: per-pixel RGB values, 3 per pixel,
+    float64}) as directory/<name>.npy.  An array above its equal share of
+    `max_bytes` is cut to a fixed sample of whole pixels (ascending pixel ids
+    drawn without replacement from a generator seeded with DUMP_SEED: the same
+    pixels in every run and for every array of that size).  Returns {name:
+    {"file", "shape", "dtype", "pixels", "of_pixels"}}."""
+    import numpy as np
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    share = max_bytes // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3)
+        npix = a.shape[0]
+        keep = share // (3 * a.itemsize)
+        if npix > keep:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(npix, size=keep, replace=False))]
+        np.save(directory / f"{name}.npy", a)
+        written[name] = {"file": f"{name}.npy", "shape": list(a.shape), "dtype": str(a.dtype),
+                         "pixels": int(a.shape[0]), "of_pixels": int(npix)}
+    return written
+
+
 # Per-rank phase times of the timed steps (ms per step): the traversal
 # kernel's HIP-event time, and render_step's wall phases (render = zero +
 # render call incl. k_reduce / k_emit, reduce = the RCCL collective,
@@ -479,7 +522,12 @@ def main():
             roof["bvh_lds_nodes"] = info["bvh_lds_nodes"]  # BVH node packet staged in LDS per workgroup
         ms_gpu = sum(s["ms_total"] for s in stats) / max(len(stats), 1)
         out = result_line(args, world, spp_total, elapsed, samples, seg, ms_gpu, roof, phases, placement)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            # what render_step left its caller after the last timed step: the per-pixel fp64
+            # radiance sums (reduced to rank 0) and the finalised canvas
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, {"accum": accum.cpu().numpy(),
+                                                                   "canvas": canvas.cpu().numpy()})
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or (os.cpu_count() or 1)
             try:
                 out["cpu_baseline"] = cpu_baseline(args, threads)

@@ -144,9 +144,11 @@ def build_cli(force: bool = False) -> Path:
 def build_oracle(force: bool = False) -> None:
     """Test-only checker (oracle/): the C restatement always; the reference
     harness only where the reference sources exist (this container)."""
-    targets = ["port"]
-    if Path(os.environ.get("RTW_REFERENCE_DIR", "/root/reference/RayTracingWeekend")).is_dir():
-        targets.append("ref")
+    # ref-if-present: `ref` where make finds the reference's sources, nothing
+    # where they are absent or not this user's to read
+    targets = ["port", "ref-if-present"]
+    if os.environ.get("RTW_REFERENCE_DIR"):
+        targets.append("REF_DIR=" + os.environ["RTW_REFERENCE_DIR"])
     if force:
         _run(["make", "-C", str(ROOT / "oracle"), "-B", *targets])
     else:

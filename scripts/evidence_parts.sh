@@ -15,6 +15,7 @@ tag=$1
 part=$2
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+out_dir=$_  # the output directory made above
 case "$part" in
 fp64)
     timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
@@ -34,8 +35,8 @@ fp32)
         --no-cpu-baseline
     ;;
 lines)
-    timeout -k 10 300 python bench.py > gpurun_out/bench_T_$tag.txt 2>&1
-    tail -1 gpurun_out/bench_T_$tag.txt | cut -c1-200
+    timeout -k 10 300 python bench.py --full > "$out_dir/bench_T_$tag.txt" 2>&1
+    tail -1 "$out_dir/bench_T_$tag.txt" | cut -c1-200
     bash scripts/bench_configs.sh $tag > /dev/null
     bash scripts/bench_fp32.sh $tag > /dev/null
     bash scripts/full_configs.sh $tag > /dev/null

@@ -9,7 +9,7 @@ tag=$1; shift
 out=gpurun_out/full_$tag.log
 mkdir -p gpurun_out; : > $out
 run() {
-    timeout -k 10 400 python bench.py --steps 1 --warmup 1 "$@" > gpurun_out/full_$tag.tmp 2>&1 \
+    timeout -k 10 400 python bench.py --full --steps 1 --warmup 1 "$@" > "${out%.log}.tmp" 2>&1 \
         || { cat gpurun_out/full_$tag.tmp; exit 1; }
     tail -1 gpurun_out/full_$tag.tmp >> $out
     tail -1 gpurun_out/full_$tag.tmp | cut -c1-400

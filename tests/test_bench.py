@@ -221,6 +221,51 @@ def test_bench_line_drops_an_unbounded_valu_figure(bench):
     assert bench.bounded_valu(dict(ok)) == ok
 
 
+def test_plain_run_leaves_the_extras_to_full(bench, monkeypatch):
+    """A plain run measures the headline only: --full (off by default) asks
+    for the CPU baseline, --no-cpu-baseline still drops it there, and --steps
+    is the number of timed steps (at least one)."""
+    a = parse(bench, monkeypatch)
+    assert a.full is False and a.dump_outputs == ""
+    b = parse(bench, monkeypatch, "--full", "--steps", "7", "--dump-outputs", "somewhere")
+    assert b.full is True and b.no_cpu_baseline is False and b.steps == 7 and b.dump_outputs == "somewhere"
+    line = bench.result_line(b, 1, b.spp, 3.5, b.nx * b.ny * b.spp * 7, 0, 0.0, None, bench.rank_phases({}, 1))
+    assert line["steps"] == 7 and line["ms_per_step"] == 500.0 and line["cpu_baseline"] is None
+    with pytest.raises(SystemExit):
+        parse(bench, monkeypatch, "--steps", "0")
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_limit(bench, tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64, whole when it
+    fits its share of the byte limit, else the same seeded sample of whole
+    pixels in every run; the files together stay under the limit."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    accum, canvas = rng.random(50 * 40 * 3), rng.random(50 * 40 * 3)
+    rec = bench.dump_outputs(tmp_path / "a" / "b", {"accum": accum, "canvas": canvas})
+    got = np.load(tmp_path / "a" / "b" / "accum.npy")
+    assert got.dtype == np.float64 and got.shape == (2000, 3) and np.array_equal(got.reshape(-1), accum)
+    assert np.array_equal(np.load(tmp_path / "a" / "b" / "canvas.npy").reshape(-1), canvas)
+    assert rec["accum"] == {"file": "accum.npy", "shape": [2000, 3], "dtype": "float64", "pixels": 2000,
+                            "of_pixels": 2000}
+    # a limit of 2 x 24 000 bytes: 1000 of the 2000 pixels of each array, the same ones in both and in every run
+    limit = 2 * 1000 * 24
+    for d in ("c", "d"):
+        rec = bench.dump_outputs(tmp_path / d, {"accum": accum, "canvas": canvas}, max_bytes=limit)
+        assert rec["canvas"]["pixels"] == 1000 and rec["canvas"]["of_pixels"] == 2000
+    s_acc, s_can = np.load(tmp_path / "c" / "accum.npy"), np.load(tmp_path / "c" / "canvas.npy")
+    assert s_acc.shape == s_can.shape == (1000, 3) and s_acc.dtype == np.float64
+    assert np.array_equal(s_acc, np.load(tmp_path / "d" / "accum.npy"))
+    pix = accum.reshape(-1, 3)
+    idx = np.array([np.flatnonzero((pix == p).all(axis=1))[0] for p in s_acc])
+    assert np.all(np.diff(idx) > 0)  # distinct pixels, ascending
+    assert np.array_equal(s_can, canvas.reshape(-1, 3)[idx])  # the same pixels of every array
+    assert s_acc.nbytes + s_can.nbytes <= limit
+    # the largest benchmarked image (C5, 1600 x 1600) stays under 64 MB in all
+    share = bench.DUMP_MAX_BYTES // 2
+    assert 2 * (share // 24 * 24 + 128) <= 64 * 1000 * 1000
+
+
 def test_shared_gpu_rehearsal_is_named_in_the_line(bench, monkeypatch):
     """RTW_BENCH_SHARED_GPU=1 (every rank on cuda:0, gloo collectives: the
     one-GPU rehearsal of the N > 1 path, tests/test_gpu_multirank.py) must
