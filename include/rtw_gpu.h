@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define RTW_ABI_VERSION 3
+#define RTW_ABI_VERSION 4
 /* Fixed by the ABI: it sizes rtw_entry (op / op_param).  A client built with
  * another value would lay entries out differently from this library. */
 #define RTW_MAX_OPS 8
@@ -148,18 +148,36 @@ typedef struct rtw_material {
     double ref_idx;
 } rtw_material; /* 48 bytes */
 
-/* texture.h:10-71 */
+/* texture.h:10-99 */
 typedef enum rtw_texture_type {
     RTW_TEX_CONSTANT = 0, /* color                                       */
     RTW_TEX_CHECKER = 1,  /* odd/even texture indices                    */
-    RTW_TEX_NOISE = 2     /* scale; needs perlin tables in the desc      */
+    RTW_TEX_NOISE = 2,    /* scale; needs perlin tables in the desc      */
+    RTW_TEX_IMAGE = 3     /* width, height, byte offset of the texels    */
 } rtw_texture_type;
 
+/* The three int fields after `type` serve two texture kinds:
+ *   RTW_TEX_CHECKER  odd, even = texture indices of the two children;
+ *   RTW_TEX_IMAGE    odd = image width nx, even = image height ny, offset =
+ *                    byte offset of the image's first texel in
+ *                    rtw_scene_desc::image_texels.  The image is 3*nx*ny
+ *                    bytes, RGB interleaved, row 0 first (image_texture,
+ *                    texture.h:73-99: texel (i, j) at offset + 3*i + 3*nx*j,
+ *                    i = int(u*nx), j = int((1-v)*ny - 0.001f), both clamped,
+ *                    each channel / 255.0).  Two textures may name the same
+ *                    texels.  (u, v) are the hit's surface coordinates: a
+ *                    rect's (a-a0)/(a1-a0), (b-b0)/(b1-b0) (hittable.h:158-159),
+ *                    a sphere's longitude / latitude (sphere.h:115-122).  An
+ *                    isotropic material (the phase function of a
+ *                    constant_medium) must not reach an image texture: the
+ *                    reference leaves (u, v) of a medium's hit unset
+ *                    (hittable.h:420-489), RTW_ERR_UNSUPPORTED.
+ * Other kinds leave them 0. */
 typedef struct rtw_texture {
     int32_t type;
     int32_t odd;
     int32_t even;
-    int32_t pad;
+    int32_t offset;
     double color[3];
     double scale;
 } rtw_texture; /* 48 bytes */
@@ -225,6 +243,11 @@ typedef struct rtw_scene_desc {
     const int32_t* visits;
     int32_t n_visits;
     int32_t pad;
+    /* The texels of every RTW_TEX_IMAGE texture, back to back (each image
+     * at its rtw_texture::offset); image_bytes = their total size in bytes.
+     * Null / 0 for a scene without image textures. */
+    const uint8_t* image_texels;
+    uint64_t image_bytes;
 } rtw_scene_desc;
 
 #define RTW_VISIT_REPLAY 0x40000000
@@ -392,7 +415,8 @@ uint32_t rtw_path_seed(uint64_t seed, uint32_t pixel, uint32_t s);
 
 /* Build one of the reference scenes with the host C++ hittable API and
  * flatten it.  names: "cornell_box", "random_balls", "dielectric",
- * "light_sample", "book2_final".  `aspect` = nx/ny (Scene/scene.h ctor arg).
+ * "light_sample", "book2_final", "textured" (a test scene of image textures
+ * on every primitive kind).  `aspect` = nx/ny (Scene/scene.h ctor arg).
  * `use_bvh` builds BVHs over the world / large groups.  The returned desc is
  * owned by the library; free it with rtw_scene_desc_free. */
 int rtw_scene_builtin(const char* name, double aspect, int use_bvh, rtw_scene_desc** out_desc);

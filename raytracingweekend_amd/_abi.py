@@ -13,7 +13,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("RTW_LIBRARY", PKG / "librtw.so"))
 
-RTW_ABI_VERSION = 3
+RTW_ABI_VERSION = 4
 RTW_MAX_OPS = 8
 
 # enums (rtw_gpu.h)
@@ -21,7 +21,7 @@ RTW_PRIM_SPHERE, RTW_PRIM_MOVING_SPHERE, RTW_PRIM_RECT_XY, RTW_PRIM_RECT_XZ, RTW
 RTW_OP_TRANSLATE, RTW_OP_ROTATE_Y, RTW_OP_FLIP = 1, 2, 3
 RTW_ENTRY_GROUP, RTW_ENTRY_MEDIUM = 0, 1
 RTW_MAT_LAMBERTIAN, RTW_MAT_METAL, RTW_MAT_DIELECTRIC, RTW_MAT_DIFFUSE_LIGHT, RTW_MAT_ISOTROPIC = range(5)
-RTW_TEX_CONSTANT, RTW_TEX_CHECKER, RTW_TEX_NOISE = range(3)
+RTW_TEX_CONSTANT, RTW_TEX_CHECKER, RTW_TEX_NOISE, RTW_TEX_IMAGE = range(4)
 RTW_LIGHT_DEFAULT, RTW_LIGHT_XZ_RECT, RTW_LIGHT_SPHERE = range(3)
 RTW_RENDER_SHADED, RTW_RENDER_NORMAL = 0, 1
 RTW_BG_BLACK, RTW_BG_GRADIENT = 0, 1
@@ -54,7 +54,7 @@ class rtw_material(C.Structure):
 
 
 class rtw_texture(C.Structure):
-    _fields_ = [("type", C.c_int32), ("odd", C.c_int32), ("even", C.c_int32), ("pad", C.c_int32),
+    _fields_ = [("type", C.c_int32), ("odd", C.c_int32), ("even", C.c_int32), ("offset", C.c_int32),
                 ("color", C.c_double * 3), ("scale", C.c_double)]
 
 
@@ -78,7 +78,8 @@ class rtw_scene_desc(C.Structure):
                 ("lights", C.POINTER(rtw_light)), ("bvh_nodes", C.POINTER(rtw_bvh_node)),
                 ("bvh_items", C.POINTER(C.c_int32)), ("perlin_ranvec", C.POINTER(C.c_double)),
                 ("perlin_perm", C.POINTER(C.c_int32)), ("camera", rtw_camera_desc),
-                ("visits", C.POINTER(C.c_int32)), ("n_visits", C.c_int32), ("pad", C.c_int32)]
+                ("visits", C.POINTER(C.c_int32)), ("n_visits", C.c_int32), ("pad", C.c_int32),
+                ("image_texels", C.POINTER(C.c_uint8)), ("image_bytes", C.c_uint64)]
 
 
 class rtw_render_params(C.Structure):

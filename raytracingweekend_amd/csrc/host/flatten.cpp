@@ -171,6 +171,10 @@ struct flattener {
     std::vector<int32_t> items;
     std::map<const material*, int> mat_ids;
     std::map<const texture*, int> tex_ids;
+    // every image_texture's pixels back to back; a byte_array shared by
+    // several textures is stored once
+    std::vector<uint8_t> texels;
+    std::map<const image_texture::byte_array*, int64_t> texel_offsets;
     std::set<int> box_starts;  // first prims of boxes' six-rect runs
     bool perlin = false;
     std::string err;
@@ -204,14 +208,41 @@ struct flattener {
             texs[id].odd = odd;
             texs[id].even = even;
             return id;
+        } else if (auto im = dynamic_cast<const image_texture*>(t)) {  // texture.h:73-99
+            if (!im->data || im->nx < 1 || im->ny < 1 ||
+                (uint64_t)im->data->size() < 3ull * (uint64_t)im->nx * (uint64_t)im->ny) {
+                err = "image_texture without pixels, or with fewer than 3 * nx * ny bytes";
+                return -1;
+            }
+            auto f = texel_offsets.find(im->data.get());
+            if (f == texel_offsets.end()) {
+                if ((uint64_t)texels.size() + im->data->size() > 0x7fffffffull) {
+                    err = "more than 2 GiB of image texels";
+                    return -1;
+                }
+                f = texel_offsets.emplace(im->data.get(), (int64_t)texels.size()).first;
+                texels.insert(texels.end(), im->data->begin(), im->data->end());
+            }
+            x.type = RTW_TEX_IMAGE;
+            x.odd = im->nx;
+            x.even = im->ny;
+            x.offset = (int32_t)f->second;
         } else {
-            err = "unsupported texture type (image_texture has no loader in this build)";
+            err = "unsupported texture type";
             return -1;
         }
         const int id = (int)texs.size();
         tex_ids[t] = id;
         texs.push_back(x);
         return id;
+    }
+
+    // Texture `id`, or a checker child below it, is an image.
+    bool reaches_image(int id, int guard = 0) const {
+        if (id < 0 || id >= (int)texs.size() || guard > (int)texs.size()) return false;
+        if (texs[id].type == RTW_TEX_IMAGE) return true;
+        if (texs[id].type != RTW_TEX_CHECKER) return false;
+        return reaches_image(texs[id].odd, guard + 1) || reaches_image(texs[id].even, guard + 1);
     }
 
     int material_id(const material* m) {
@@ -240,6 +271,12 @@ struct flattener {
         } else if (auto is = dynamic_cast<const isotropic*>(m)) {
             x.type = RTW_MAT_ISOTROPIC;
             x.texture = texture_id(is->albedo.get());
+            // constant_medium::hit sets no rec.u / rec.v (hittable.h:420-489):
+            // the reference's isotropic would look an image up at
+            // indeterminate coordinates
+            if (err.empty() && reaches_image(x.texture))
+                err = "an isotropic material (constant_medium) with an image_texture is unsupported: the "
+                      "reference's medium hit leaves (u, v) unset (hittable.h:420-489)";
         } else {
             err = "unsupported material type";
             return -1;
@@ -693,6 +730,10 @@ int rtw_flatten_world(const hittable_list& world, const hittable_list* lights, c
         d->perlin_ranvec = rtw_dup(rv);
         d->perlin_perm = rtw_dup(pm);
     }
+    if (!f.texels.empty()) {
+        d->image_texels = rtw_dup(f.texels);
+        d->image_bytes = (uint64_t)f.texels.size();
+    }
     d->camera = cam.desc();
     *out = d;
     return RTW_OK;
@@ -710,6 +751,7 @@ extern "C" void rtw_scene_desc_free(rtw_scene_desc* d) {
     free((void*)d->perlin_ranvec);
     free((void*)d->perlin_perm);
     free((void*)d->visits);
+    free((void*)d->image_texels);
     delete d;
 }
 

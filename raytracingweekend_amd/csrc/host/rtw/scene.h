@@ -62,9 +62,20 @@ public:
     explicit nested_scene(double aspect, bool media = true);
 };
 
+// Test scene for image textures (not in the reference, whose scenes use
+// none): two images computed in code on every primitive kind (scenes.cpp).
+// `first`, when given, replaces the first image (nx * ny RGB texels).
+class textured_scene : public scene {
+public:
+    explicit textured_scene(double aspect, std::shared_ptr<image_texture::byte_array> first = nullptr, int nx = 0,
+                            int ny = 0);
+    // the scene's own images: 0 = 7 x 5, 1 = 4 x 3
+    static std::shared_ptr<image_texture::byte_array> test_image(int which, int& nx, int& ny);
+};
+
 // Builds a scene by name ("cornell_box", "random_balls", "dielectric",
-// "light_sample", "book2_final", "nested", "nested_plain"); nullptr for an
-// unknown name.
+// "light_sample", "book2_final", "nested", "nested_plain", "textured");
+// nullptr for an unknown name.
 std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect);
 
 // Flatten the hittable graph of `sc` into a library-owned rtw_scene_desc

@@ -1,5 +1,5 @@
 // texture.h / noise.h surface of the host scene API.
-// Reference: texture.h:10-71 (constant, checker, noise) and noise.h:9-225
+// Reference: texture.h:10-99 (constant, checker, noise, image) and noise.h:9-225
 // (Perlin lattice noise and its tables).  value(), noise() and turb() are
 // evaluated on the host with the reference's arithmetic (IEEE fp64, glibc
 // sin); the device kernels have their own restatement for renders and read
@@ -8,6 +8,8 @@
 #pragma once
 #include <cmath>
 #include <memory>
+#include <string>
+#include <vector>
 #include "vec3.h"
 
 class texture {
@@ -99,3 +101,41 @@ public:
     perlin noise;
     double scale;
 };
+
+// texture.h:73-99: nearest-texel lookup in an RGB byte image, row 0 at v = 1.
+// The column is int(u nx), the row int((1 - v) ny - 0.001f) (the float
+// literal widened to double), both clamped to the image; a NaN or
+// out-of-range product converts to INT_MIN on x86-64 (cvttsd2si) and clamps
+// to 0.  Texel (i, j) is data[3 i + 3 nx j ..+2], each channel / 255.0.
+class image_texture : public texture {
+public:
+    typedef unsigned char byte;
+    typedef std::vector<byte> byte_array;
+
+    image_texture() {}
+    image_texture(std::shared_ptr<byte_array> pixels, int A, int B) : data(pixels), nx(A), ny(B) {}
+    vec3 value(double u, double v, const vec3&) const override {
+        const int i = texel_index(u * nx, nx);
+        const int j = texel_index((1 - v) * ny - 0.001f, ny);
+        const byte* t = data->data() + 3 * i + 3 * nx * j;
+        return vec3(int(t[0]) / 255.0, int(t[1]) / 255.0, int(t[2]) / 255.0);
+    }
+    // (int)x as x86-64 converts it, then clamp to [0, n - 1]
+    static int texel_index(double x, int n) {
+        const int k = (x == x && x < 2147483648.0 && x > -2147483649.0) ? (int)x : (int)0x80000000u;
+        return k < 0 ? 0 : (k > n - 1 ? n - 1 : k);
+    }
+
+    std::shared_ptr<byte_array> data;
+    int nx = 0;
+    int ny = 0;
+};
+
+// Read a PPM image (binary P6 or ASCII P3, maxval 255, '#' comments in the
+// header) into RGB bytes, row 0 first -- the layout image_texture reads.  The
+// reference has no image loader (its image_texture takes pixels from the
+// caller); this is the library's own (image_io.cpp).  Returns 0, or a
+// negative rtw_status with the reason in rtw_last_error(): an unreadable
+// file, another magic, another maxval, a size below 1 or above 2^24 texels a
+// side, a truncated or malformed body.
+int rtw_load_ppm(const std::string& path, image_texture::byte_array& pixels, int& nx, int& ny);

@@ -276,6 +276,69 @@ nested_scene::nested_scene(double aspect, bool media) {
     background_type = BackgroundType::Black;
 }
 
+// The test images of the textured scene: every texel its own colour, no
+// symmetry (37 and 53 are odd, so k -> 37 k + c and k -> 53 k + c are
+// one-to-one modulo 256 and the red channels alone tell the texels apart).
+std::shared_ptr<image_texture::byte_array> textured_scene::test_image(int which, int& nx, int& ny) {
+    nx = which == 0 ? 7 : 4;
+    ny = which == 0 ? 5 : 3;
+    auto px = std::make_shared<image_texture::byte_array>((size_t)3 * nx * ny);
+    for (int j = 0; j < ny; ++j)
+        for (int i = 0; i < nx; ++i) {
+            const int k = i + nx * j;
+            image_texture::byte* t = px->data() + 3 * k;
+            if (which == 0) {
+                t[0] = (image_texture::byte)((37 * k + 11) & 255);
+                t[1] = (image_texture::byte)((91 * k + 5 * i + 40) & 255);
+                t[2] = (image_texture::byte)((255 - 7 * k - 13 * j * j) & 255);
+            } else {
+                t[0] = (image_texture::byte)((53 * k + 200) & 255);
+                t[1] = (image_texture::byte)((29 * k + 17 * j + 90) & 255);
+                t[2] = (image_texture::byte)((19 * k * k + 3 * i + 60) & 255);
+            }
+        }
+    return px;
+}
+
+// Image textures on every primitive kind under a gradient sky (no medium, no
+// light list): a checker ground whose even child is the first image; that
+// image on a sphere, a moving sphere, a hollow (negative-radius) sphere, a
+// flipped ceiling rect and an emitting xy_rect whose normal points away from
+// the camera (diffuse_light emits where dot(normal, ray) > 0); the second
+// image, of another size, on a rotated, translated box (all three rect
+// kinds) and one more ball.  Ten world objects, so use_bvh builds a world BVH.
+textured_scene::textured_scene(double aspect, std::shared_ptr<image_texture::byte_array> first, int fnx, int fny) {
+    int ax = fnx, ay = fny, bx = 0, by = 0;
+    auto pa = first ? first : test_image(0, ax, ay);
+    auto pb = test_image(1, bx, by);
+    tex_ptr img_a = std::make_shared<image_texture>(pa, ax, ay);
+    tex_ptr img_b = std::make_shared<image_texture>(pb, bx, by);
+    tex_ptr grey = solid(0.3, 0.3, 0.35);
+    tex_ptr tiles = std::make_shared<checker_texture>(img_a, grey);  // even = the image
+    auto mat_a = std::make_shared<lambertian>(img_a);
+    auto mat_b = std::make_shared<lambertian>(img_b);
+
+    Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, std::make_shared<lambertian>(tiles)));
+    Add(std::make_shared<sphere>(vec3(0, 1, 0), 1.0, mat_a));
+    auto mover = std::make_shared<moving_sphere>(vec3(-2.5, 0.6, -1.0), 0.6, mat_a);
+    movement_linear path;
+    path.center1 = vec3(-2.5, 1.0, -1.0);
+    path.time0 = 0.0;
+    path.time1 = 1.0;
+    mover->set_movement(path);
+    Add(mover);
+    Add(std::make_shared<sphere>(vec3(2.5, 0.9, -0.5), -0.9, mat_a));
+    auto crate = std::make_shared<box>(vec3(0, 0, 0), vec3(1.0, 1.5, 1.0), mat_b);
+    Add(std::make_shared<translate>(std::make_shared<rotate_y>(crate, 25.0), vec3(-1.2, 0.0, 2.5)));
+    Add(std::make_shared<flip_normals>(std::make_shared<xz_rect>(-2.0, 2.0, -2.0, 2.0, 3.5, mat_a)));
+    Add(std::make_shared<xy_rect>(-1.75, 1.75, 0.25, 2.75, 4.0, std::make_shared<diffuse_light>(img_a)));
+    Add(std::make_shared<sphere>(vec3(1.6, 0.4, -2.0), 0.4, mat_b));
+    Add(std::make_shared<sphere>(vec3(-0.9, 0.3, -2.6), 0.3, diffuse(0.7, 0.2, 0.2)));
+    Add(std::make_shared<sphere>(vec3(3.4, 0.5, 2.2), 0.5, std::make_shared<metal>(vec3(0.8, 0.8, 0.7), 0.1)));
+
+    cam = look(vec3(0.5, 2.0, -9.0), vec3(0.0, 1.2, 0.0), 35.0, aspect, 0.0, 10.0);
+}
+
 std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect) {
     if (name == "nested") return std::make_unique<nested_scene>(aspect);
     if (name == "nested_plain") return std::make_unique<nested_scene>(aspect, false);
@@ -284,5 +347,6 @@ std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect
     if (name == "dielectric") return std::make_unique<dielectric_scene>(aspect);
     if (name == "light_sample") return std::make_unique<light_sample>(aspect);
     if (name == "book2_final") return std::make_unique<book2_final_scene>(aspect);
+    if (name == "textured") return std::make_unique<textured_scene>(aspect);
     return nullptr;
 }

@@ -19,7 +19,7 @@ int validate_desc(const rtw_scene_desc* d) {
     if ((d->n_entries && !d->entries) || (d->n_prims && !d->prims) || (d->n_materials && !d->materials) ||
         (d->n_textures && !d->textures) || (d->n_lights && !d->lights) || (d->n_bvh_nodes && !d->bvh_nodes) ||
         (d->n_bvh_items && !d->bvh_items) || (d->n_visits && !d->visits) ||
-        (d->has_perlin && (!d->perlin_ranvec || !d->perlin_perm)))
+        (d->has_perlin && (!d->perlin_ranvec || !d->perlin_perm)) || (d->image_bytes && !d->image_texels))
         return rtw_fail(RTW_ERR_INVALID, "null array with a nonzero count in scene desc");
     for (int e = 0; e < d->n_entries; ++e) {
         const rtw_entry& E = d->entries[e];
@@ -78,6 +78,40 @@ int validate_desc(const rtw_scene_desc* d) {
         if (T.type == RTW_TEX_NOISE && !d->has_perlin) return rtw_fail(RTW_ERR_INVALID, "noise texture without perlin tables");
         if (T.type == RTW_TEX_CHECKER && (T.odd < 0 || T.odd >= d->n_textures || T.even < 0 || T.even >= d->n_textures))
             return rtw_fail(RTW_ERR_INVALID, "checker child out of range");
+        if (T.type < RTW_TEX_CONSTANT || T.type > RTW_TEX_IMAGE) return rtw_fail(RTW_ERR_INVALID, "bad texture type");
+        if (T.type == RTW_TEX_IMAGE) {
+            // width = odd, height = even (rtw_gpu.h); the image's 3*nx*ny
+            // bytes lie inside the texel block (64-bit: no overflow)
+            if (T.odd < 1 || T.even < 1)
+                return rtw_fail(RTW_ERR_INVALID, "image texture " + std::to_string(t) + ": size below 1");
+            if (!d->image_texels)
+                return rtw_fail(RTW_ERR_INVALID, "image texture " + std::to_string(t) + ": null texel pointer");
+            const uint64_t need = 3ull * (uint64_t)T.odd * (uint64_t)T.even;
+            if (T.offset < 0 || (uint64_t)T.offset > d->image_bytes || need > d->image_bytes - (uint64_t)T.offset)
+                return rtw_fail(RTW_ERR_INVALID, "image texture " + std::to_string(t) + ": texels out of bounds");
+        }
+    }
+    // An isotropic material (a medium's phase function) must not reach an
+    // image texture, directly or through checkers: the reference's medium hit
+    // sets no (u, v) (hittable.h:420-489).
+    {
+        auto reaches_image = [&](int root) {
+            std::vector<char> seen(d->n_textures, 0);
+            std::vector<int> todo{root};
+            while (!todo.empty()) {
+                const int t = todo.back();
+                todo.pop_back();
+                if (seen[t]++) continue;
+                const rtw_texture& T = d->textures[t];
+                if (T.type == RTW_TEX_IMAGE) return true;
+                if (T.type == RTW_TEX_CHECKER) todo.push_back(T.odd), todo.push_back(T.even);
+            }
+            return false;
+        };
+        for (int m = 0; m < d->n_materials; ++m)
+            if (d->materials[m].type == RTW_MAT_ISOTROPIC && reaches_image(d->materials[m].texture))
+                return rtw_fail(RTW_ERR_UNSUPPORTED, "material " + std::to_string(m) +
+                                                         ": an isotropic material cannot use an image texture");
     }
     for (int l = 0; l < d->n_lights; ++l) {
         const rtw_light& L = d->lights[l];

@@ -385,6 +385,9 @@ struct scene {
     const node_store* lnodes;
     int32_t n_lnodes;
     int32_t n_nodes;  // device BVH nodes in all
+    // the texels of the image textures (rtw_scene_desc::image_texels), in
+    // global memory: read by the SF_IMAGE kernels only
+    const uint8_t* texels;
 };
 
 // Scene features a traversal kernel is specialised for.
@@ -1516,8 +1519,12 @@ RTW_D hit_state world_closest(const scene& S, const ray& r, uint32_t& rng) {
 // the reference produced it (leaf hit, then ops outward).
 // (MEDIA false: the scene has no isotropic material, hence no medium whose
 // hit this could be.)
-template <bool MEDIA = true, bool STATIC = false>
-RTW_D void hit_record(const scene& S, const ray& r, const hit_state& h, d3& p, d3& n, int& mat, bool& rect) {
+// UV (kernels of scenes with image textures, SF_IMAGE): `sl` receives what
+// the winner's surface coordinates are formed from, in the prim's own frame
+// -- a rect's hit point before the entry's ops, a sphere's normal (p - c) /
+// radius before the prim's flip and the entry's ops (image_uv below).
+template <bool MEDIA = true, bool STATIC = false, bool UV = false>
+RTW_D void hit_record(const scene& S, const ray& r, const hit_state& h, d3& p, d3& n, int& mat, bool& rect, d3& sl) {
     rect = false;
     if (MEDIA && h.prim <= -2) {  // constant_medium, hittable.h:469-472, then its enclosing ops outward
         const entry_v e = view_entry<false>(S, -h.prim - 2);
@@ -1536,13 +1543,20 @@ RTW_D void hit_record(const scene& S, const ray& r, const hit_state& h, d3& p, d
     if (is_sphere(q.type)) {
         const d3 cc = STATIC ? ld3(q.p) : sphere_center(q, lr.t, motion_frac(S, lr.t, q.type >= DP_MOVING_COMMON));
         n = (p - cc) / q.p[3];
+        if (UV) sl = n;
     } else {
         n = rect_normal(q.type);
         rect = true;
+        if (UV) sl = p;
     }
     if (q.flip & 1) n = -n;
     entry_rec_out<false>(e, p, n);
     mat = q.material;
+}
+template <bool MEDIA = true, bool STATIC = false>
+RTW_D void hit_record(const scene& S, const ray& r, const hit_state& h, d3& p, d3& n, int& mat, bool& rect) {
+    d3 sl;
+    hit_record<MEDIA, STATIC, false>(S, r, h, p, n, mat, rect, sl);
 }
 
 // ------------------------------------------------------------------ textures
@@ -1582,13 +1596,67 @@ RTW_D double turb(const scene& S, d3 p) {  // noise.h:74-86
 }
 
 // Shade-kernel specialisation by the scene's material / texture set.
-enum : int { SF_NOISE = 1, SF_CHECKER = 2, SF_METAL = 4, SF_DIEL = 8, SF_ISO = 16, SF_ALL = 31 };
+// SF_ALL: every material and every texture but the image texture (its value
+// is part of the kernels' names); SF_IMAGE: the scene holds image textures,
+// so shading forms surface coordinates (u, v) where a texture walk reaches
+// one -- only kernels compiled with this bit carry that code.
+enum : int { SF_NOISE = 1, SF_CHECKER = 2, SF_METAL = 4, SF_DIEL = 8, SF_ISO = 16, SF_ALL = 31, SF_IMAGE = 32 };
 
+// (int)x as x86-64 converts (cvttsd2si: truncation; NaN / out of range ->
+// INT_MIN), as rtw_quantize_canvas_device.
+RTW_D int32_t cvt_x86(double x) {
+    return (x == x && x < 2147483648.0 && x > -2147483649.0) ? (int32_t)x : (int32_t)0x80000000u;
+}
+// ocml's atan2 / asin out of line (their polynomial constants stay out of
+// the shading loop's registers, as sin_far's); a few ulps from glibc's
+__device__ __attribute__((noinline)) void sphere_uv_far(double nx, double ny, double nz, double& u, double& v) {
+    // sphere.h:115-122
+    const double phi = atan2(nz, nx);
+    const double theta = asin(ny);
+    u = 1 - (phi + kPi) / kTwoPi;
+    v = (theta + kPi / 2) / kPi;
+}
+// Surface coordinates of the hit of prim `prim` from hit_record's `sl`:
+// rects (a - a0) / (a1 - a0), (b - b0) / (b1 - b0) of the local hit point
+// (hittable.h:158-159, 193-194, 250-251; the host's very sums and IEEE
+// quotients: bit-identical), spheres longitude / latitude of the local
+// normal.  A medium's hit has none (prim < 0; validate_desc keeps images away
+// from isotropic materials).
+RTW_D void image_uv(const scene& S, int prim, d3 sl, double& u, double& v) {
+    u = 0, v = 0;
+    if (prim < 0) return;
+    const rtw_prim& q = S.prims[prim];
+    if (is_sphere(q.type)) {
+        sphere_uv_far(sl.x, sl.y, sl.z, u, v);
+        return;
+    }
+    const double a = q.type == RTW_PRIM_RECT_YZ ? sl.y : sl.x;
+    const double b = q.type == RTW_PRIM_RECT_XY ? sl.y : sl.z;
+    u = (a - q.p[0]) / (q.p[1] - q.p[0]);
+    v = (b - q.p[2]) / (q.p[3] - q.p[2]);
+}
+// image_texture::value (texture.h:81-94); odd / even = the image's nx / ny
+RTW_D d3 image_value(const scene& S, const rtw_texture& t, double u, double v) {
+    const int nx = t.odd, ny = t.even;
+    int i = cvt_x86(u * nx);
+    int j = cvt_x86((1 - v) * ny - (double)0.001f);
+    i = i < 0 ? 0 : (i > nx - 1 ? nx - 1 : i);
+    j = j < 0 ? 0 : (j > ny - 1 ? ny - 1 : j);
+    const uint8_t* px = S.texels + (size_t)(uint32_t)t.offset + 3 * (size_t)i + 3 * (size_t)nx * (size_t)j;
+    return d3{(double)(int)px[0] / 255.0, (double)(int)px[1] / 255.0, (double)(int)px[2] / 255.0};
+}
+
+// prim, sl: the hit's prim and hit_record's `sl` (read with SF_IMAGE only)
 template <int M>
-RTW_D d3 texture_value(const scene& S, int id, d3 p) {
+RTW_D d3 texture_value(const scene& S, int id, d3 p, int prim = -1, d3 sl = d3{0, 0, 0}) {
     for (int guard = 0; guard < 8; ++guard) {
         const rtw_texture& t = S.textures[id];
-        if (!(M & (SF_NOISE | SF_CHECKER)) || t.type == RTW_TEX_CONSTANT) return ld3(t.color);
+        if (!(M & (SF_NOISE | SF_CHECKER | SF_IMAGE)) || t.type == RTW_TEX_CONSTANT) return ld3(t.color);
+        if ((M & SF_IMAGE) && t.type == RTW_TEX_IMAGE) {
+            double u, v;
+            image_uv(S, prim, sl, u, v);
+            return image_value(S, t, u, v);
+        }
         if ((M & SF_CHECKER) && t.type == RTW_TEX_CHECKER) {  // texture.h:38-49
             const double sines = sin_tex(10.0 * p.x) * sin_tex(10.0 * p.y) * sin_tex(10.0 * p.z);
             id = sines < 0 ? t.odd : t.even;

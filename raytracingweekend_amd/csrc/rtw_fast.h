@@ -88,10 +88,10 @@ struct mat32 {
     int32_t pad;
 };  // 40 B
 struct tex32 {
-    int32_t type, odd, even;
+    int32_t type, odd, even;  // RTW_TEX_IMAGE: odd / even = the image's nx / ny
     float scale;
     float color[3];
-    int32_t pad;
+    int32_t offset;  // RTW_TEX_IMAGE: byte offset of its first texel in fscene::texels
 };  // 32 B
 
 struct fscene {
@@ -117,6 +117,7 @@ struct fscene {
     // nodes of the BFS numbering, set by the kernel; 0 elsewhere)
     const rtwd::node_store* lnodes;
     int32_t n_lnodes;
+    const uint8_t* texels;  // the image textures' texels (rtwd::scene::texels)
 };
 
 // uniform (scalar) loads of a prim's fields
@@ -591,7 +592,11 @@ RTW_D fhit world_closest(const fscene& S, const fray& r, uint32_t& rng, STK& stk
 }
 
 // the hit record of the winner (leaf hit, then ops outward)
-RTW_D void hit_record(const fscene& S, const fray& r, const fhit& h, f3& p, f3& n, int& mat, int& frame_prim) {
+// UV (scenes with image textures): `sl` receives what the surface
+// coordinates come from, as rtwd::hit_record's -- a rect's local hit point, a
+// sphere's local normal before flips and ops.
+template <bool UV = false>
+RTW_D void hit_record(const fscene& S, const fray& r, const fhit& h, f3& p, f3& n, int& mat, int& frame_prim, f3& sl) {
     frame_prim = -1;
     if (h.prim <= -2) {
         const ent_v e = view_entry<false>(S, -h.prim - 2);
@@ -610,9 +615,11 @@ RTW_D void hit_record(const fscene& S, const fray& r, const fhit& h, f3& p, f3& 
     const int type = q.type;
     if (rtwd::is_sphere(type)) {
         n = (p - sphere_center(q, lr.t)) * rcp(q.p[3]);
+        if (UV) sl = n;
     } else {
         n = rect_normal(type);
         frame_prim = h.prim;
+        if (UV) sl = p;
     }
     if (q.flip & 1) n = -n;
     ops_out<false>(e, e.n_ops, p, n);
@@ -652,11 +659,46 @@ RTW_D float turb(const float* ranvec, const int32_t* perm, f3 p) {  // noise.h:7
 // the widest register peak of the fp32 kernels, and inlined they set the
 // register budget of every path -- the list kernel spilled in shading for it
 // though Cornell has no noise texture)
-template <bool NOISE = true>
-RTW_D f3 texture_value(const fscene& S, int id, f3 p) {
+// IMAGE = true: the scene has image textures (kernels for other scenes
+// compile the lookup and the surface coordinates out).  image_texture::value
+// (texture.h:81-94) in single precision: (u, v) from the hit's prim and
+// hit_record's `sl` -- rects (hittable.h:158-159), spheres (sphere.h:115-122)
+// -- then the nearest texel's bytes / 255.
+RTW_D f3 image_value(const fscene& S, const tex32& t, int prim, f3 sl) {
+    float u = 0, v = 0;
+    if (prim >= 0) {
+        const prim32& q = S.prims[prim];
+        const int type = q.type;
+        if (rtwd::is_sphere(type)) {
+            const float phi = atan2f(sl.z, sl.x);
+            const float theta = asinf(sl.y);
+            u = 1 - (phi + kPiF) * (0.5f / kPiF);
+            v = (theta + 0.5f * kPiF) * (1.0f / kPiF);
+        } else {
+            const float a = type == RTW_PRIM_RECT_YZ ? sl.y : sl.x;
+            const float b = type == RTW_PRIM_RECT_XY ? sl.y : sl.z;
+            u = (a - q.p[0]) * rcp(q.p[1] - q.p[0]);
+            v = (b - q.p[2]) * rcp(q.p[3] - q.p[2]);
+        }
+    }
+    const int nx = t.odd, ny = t.even;
+    // NaN -> 0 (the reference's INT_MIN clamps to 0), then the clamp
+    const float fi = u * nx, fj = (1 - v) * ny - 0.001f;
+    int i = fi == fi ? (int)__builtin_fminf(__builtin_fmaxf(fi, 0.0f), (float)(nx - 1)) : 0;
+    int j = fj == fj ? (int)__builtin_fminf(__builtin_fmaxf(fj, 0.0f), (float)(ny - 1)) : 0;
+    i = i > nx - 1 ? nx - 1 : i;  // (float)(n - 1) may round up for n > 2^24
+    j = j > ny - 1 ? ny - 1 : j;
+    const uint8_t* px = S.texels + (size_t)(uint32_t)t.offset + 3 * (size_t)i + 3 * (size_t)nx * (size_t)j;
+    return f3{(float)px[0], (float)px[1], (float)px[2]} * (1.0f / 255.0f);
+}
+template <bool NOISE = true, bool IMAGE = false>
+RTW_D f3 texture_value(const fscene& S, int id, f3 p, int prim = -1, f3 sl = f3{0, 0, 0}) {
     for (int guard = 0; guard < 8; ++guard) {
         const tex32& t = S.textures[id];
         if (t.type == RTW_TEX_CONSTANT) return ldf3(t.color);
+        if constexpr (IMAGE) {
+            if (t.type == RTW_TEX_IMAGE) return image_value(S, t, prim, sl);
+        }
         if (t.type == RTW_TEX_CHECKER) {  // texture.h:38-49
             const float sines = __sinf(10 * p.x) * __sinf(10 * p.y) * __sinf(10 * p.z);
             id = sines < 0 ? t.odd : t.even;
@@ -759,7 +801,7 @@ struct seg_f {
     f3 w;
     fray next;
 };
-template <bool NOISE = true>
+template <bool NOISE = true, bool IMAGE = false>
 RTW_D seg_f shade(const fscene& S, const fray& r, const fhit& h, uint32_t& rng, uint32_t depth) {
     seg_f o{false, f3{0, 0, 0}, r};
     if (h.prim == -1) {  // background :141-159
@@ -769,9 +811,9 @@ RTW_D seg_f shade(const fscene& S, const fray& r, const fhit& h, uint32_t& rng, 
         }
         return o;
     }
-    f3 p, n;
+    f3 p, n, sl{0, 0, 0};
     int mat, fp;
-    hit_record(S, r, h, p, n, mat, fp);
+    hit_record<IMAGE>(S, r, h, p, n, mat, fp, sl);
     if (S.render_type == RTW_RENDER_NORMAL) {  // :135-136
         o.w = (n + f3{1, 1, 1}) * 0.5f;
         return o;
@@ -788,7 +830,7 @@ RTW_D seg_f shade(const fscene& S, const fray& r, const fhit& h, uint32_t& rng, 
         return S.materials[m];
     };
     if (type == RTW_MAT_DIFFUSE_LIGHT) {  // material.h:232-244, one-sided
-        if (dot(n, r.d) > 0) o.w = texture_value<NOISE>(S, tex, p);
+        if (dot(n, r.d) > 0) o.w = texture_value<NOISE, IMAGE>(S, tex, p, h.prim, sl);
         return o;
     }
     f3 f{1, 1, 1}, dir;
@@ -825,7 +867,7 @@ RTW_D seg_f shade(const fscene& S, const fray& r, const fhit& h, uint32_t& rng, 
         dir = u01(rng) < reflect_prob ? reflect(r.d, n) : refracted;
     } else if (type == RTW_MAT_ISOTROPIC) {  // material.h:257-262
         dir = random_in_unit_sphere(rng);
-        f = texture_value<NOISE>(S, tex, p);
+        f = texture_value<NOISE, IMAGE>(S, tex, p, h.prim, sl);
     } else {  // lambertian material.h:81-119 + RayTracingWeekend.cpp:112-132
         const onbf fr = frame(S, n, fp);
         float pdf_val;
@@ -842,7 +884,7 @@ RTW_D seg_f shade(const fscene& S, const fray& r, const fhit& h, uint32_t& rng, 
         if (!(pdf_val > 0)) return o;  // :126-127 returns emitted (0)
         const float cosine = dot(n, normalize(dir));
         const float spdf = cosine < 0 ? 0.0f : cosine * (1.0f / kPiF);
-        f = texture_value<NOISE>(S, tex, p) * (spdf * rcp(pdf_val));
+        f = texture_value<NOISE, IMAGE>(S, tex, p, h.prim, sl) * (spdf * rcp(pdf_val));
     }
     if (depth <= 1) return o;  // the next color() call has depth 0: returns 0
     o.cont = true;

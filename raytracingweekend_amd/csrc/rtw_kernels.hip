@@ -459,10 +459,10 @@ __device__ __forceinline__ int shade_core(const scene& S, path_st& x, double t, 
         sk.end(BLACK ? d3{0, 0, 0} : background(S, r.d));
         return SEG_END;
     }
-    d3 p, n;
+    d3 p, n, sl{0, 0, 0};  // sl: what (u, v) come from, SF_IMAGE kernels only
     int mat;
     bool rect;
-    hit_record<(M & SF_ISO) != 0, STATIC>(S, r, hit_state{t, prim, false}, p, n, mat, rect);
+    hit_record<(M & SF_ISO) != 0, STATIC, (M & SF_IMAGE) != 0>(S, r, hit_state{t, prim, false}, p, n, mat, rect, sl);
     if (!BLACK && S.render_type == RTW_RENDER_NORMAL) {  // :135-136
         sk.end(d3{0.5f, 0.5f, 0.5f} * (n + d3{1, 1, 1}));
         return SEG_END;
@@ -474,7 +474,7 @@ __device__ __forceinline__ int shade_core(const scene& S, path_st& x, double t, 
             sk.end_zero();
             return SEG_END_ZERO;
         }
-        sk.end(texture_value<M>(S, m.texture, p));
+        sk.end(texture_value<M>(S, m.texture, p, prim, sl));
         return SEG_END;
     } else if ((M & SF_METAL) && m.type == RTW_MAT_METAL) {  // material.h:128-136
         const d3 reflected = reflect(normalize(r.d), n);
@@ -501,7 +501,7 @@ __device__ __forceinline__ int shade_core(const scene& S, path_st& x, double t, 
         return scatter(d3{1.0, 1.0, 1.0}, p, dir);
     } else if ((M & SF_ISO) && m.type == RTW_MAT_ISOTROPIC) {  // material.h:257-262
         const d3 dir = random_in_unit_sphere(rng);
-        return scatter(texture_value<M>(S, m.texture, p), p, dir);
+        return scatter(texture_value<M>(S, m.texture, p, prim, sl), p, dir);
     } else {  // lambertian material.h:81-119 + RayTracingWeekend.cpp:112-132
         // (RTW_RADIANCE_FAST: quantities that only scale radiance -- the
         // attenuation / pdf factor and the pdfs' magnitudes -- are formed with
@@ -541,7 +541,7 @@ __device__ __forceinline__ int shade_core(const scene& S, path_st& x, double t, 
 #if RTW_RADIANCE_FAST
         // attenuation * scattering_pdf / pdf_val as one scalar quotient
         const double w = cosine < 0 ? 0 : rad_div(cosine, kPi * pdf_val);
-        return scatter(texture_value<M>(S, m.texture, p) * w, p, dir);
+        return scatter(texture_value<M>(S, m.texture, p, prim, sl) * w, p, dir);
 #elif RTW_STRICT_RADIANCE
         // the reference's ((attenuation * scattering_pdf) * color) / pdf_val
         // (RayTracingWeekend.cpp:129-132): m and pdf_val go to the path's
@@ -551,13 +551,13 @@ __device__ __forceinline__ int shade_core(const scene& S, path_st& x, double t, 
             sk.end_zero();
             return SEG_END_ZERO;
         }
-        sk.cont_mp(texture_value<M>(S, m.texture, p) * spdf, pdf_val, ray{p, dir, r.t});
+        sk.cont_mp(texture_value<M>(S, m.texture, p, prim, sl) * spdf, pdf_val, ray{p, dir, r.t});
         x.rng = rng;
         x.depth = depth - 1;
         return SEG_CONTINUE;
 #else
         const double spdf = cosine < 0 ? 0 : cosine / kPi;
-        return scatter((texture_value<M>(S, m.texture, p) * spdf) / pdf_val, p, dir);
+        return scatter((texture_value<M>(S, m.texture, p, prim, sl) * spdf) / pdf_val, p, dir);
 #endif
     }
 }
@@ -1278,6 +1278,10 @@ __device__ __forceinline__ const fast_args& fast_args_now() {
 // fp32 kernels for scenes without a noise texture (F bit, fast kernels only):
 // the marble texture compiled out of shading (rtw_fast.h texture_value)
 constexpr int FF_NONOISE = 1 << 12;
+// ... and for scenes with image textures: the texel lookup and the surface
+// coordinates compiled in (rtw_fast.h image_value); without this bit no fp32
+// kernel carries them
+constexpr int FF_IMAGE = 1 << 13;
 
 // Waves per SIMD of k_fast.  With the node packet, 8 waves in two
 // 1 024-thread workgroups per CU (each with a ~48 KB packet) beat 6 waves in
@@ -1297,6 +1301,7 @@ __global__ __launch_bounds__(rtwf::fast_block(F)) __attribute__((amdgpu_waves_pe
 void k_fast(fast_args) {
     using namespace rtwf;
     constexpr bool NOISE = (F & FF_NONOISE) == 0;
+    constexpr bool IMAGE = (F & FF_IMAGE) != 0;
     constexpr int kFB = fast_block(F);
     constexpr int kFW = kFB / 64;
     extern __shared__ __attribute__((aligned(16))) char s_nodes[];
@@ -1374,7 +1379,7 @@ void k_fast(fast_args) {
         }
         ++segs;
         // one segment of color() (RayTracingWeekend.cpp:52-159)
-        const seg_f sg = shade<NOISE>(fast_args_now().S, r, h, rng, depth);
+        const seg_f sg = shade<NOISE, IMAGE>(fast_args_now().S, r, h, rng, depth);
         bool end = !sg.cont;
         f3 L{0, 0, 0};
         if (sg.cont) {
@@ -2240,6 +2245,8 @@ int upload_scene(handle_t* h, const rtw_scene_desc* d) {
         {runs.data(), sizeof(world_run) * runs.size(), 0},
         {ysph.data(), sizeof(float) * ysph.size(), 0},
         {boxes64.data(), sizeof(double) * boxes64.size(), 0},
+        // the image textures' texels (validate_desc: every image inside them)
+        {d->image_texels, (size_t)d->image_bytes, 0},
     };
     size_t total = 0;
     for (auto& p : parts) {
@@ -2272,6 +2279,7 @@ int upload_scene(handle_t* h, const rtw_scene_desc* d) {
     S.runs = (const world_run*)at(13);
     S.ysph = (const float*)at(14);
     S.boxes = (const double*)at(15);
+    S.texels = (const uint8_t*)at(16);
     S.ysb_cx = ysb[0], S.ysb_cy = ysb[1], S.ysb_dy = ysb[2], S.ysb_cz = ysb[3], S.ysb_r2 = ysb[4];
     S.n_runs = (int32_t)runs.size();
     S.mv_common = mv_common ? 1 : 0;
@@ -2321,7 +2329,7 @@ int upload_scene(handle_t* h, const rtw_scene_desc* d) {
     }
     for (int k = 0; k < d->n_textures; ++k) {
         const int t = d->textures[k].type;
-        m |= t == RTW_TEX_NOISE ? SF_NOISE : t == RTW_TEX_CHECKER ? SF_CHECKER : 0;
+        m |= t == RTW_TEX_NOISE ? SF_NOISE : t == RTW_TEX_CHECKER ? SF_CHECKER : t == RTW_TEX_IMAGE ? SF_IMAGE : 0;
     }
     h->shade_mask = m;
     // BVH stack depth: a walk pushes two children per inner node and pops
@@ -2415,6 +2423,7 @@ int upload_scene(handle_t* h, const rtw_scene_desc* d) {
             tex32& o = t32[k];
             std::memset(&o, 0, sizeof o);
             o.type = T.type, o.odd = T.odd, o.even = T.even, o.scale = (float)T.scale;
+            o.offset = T.offset;  // RTW_TEX_IMAGE: odd / even = nx / ny, texels at S.texels + offset
             for (int j = 0; j < 3; ++j) o.color[j] = (float)T.color[j];
         }
         std::vector<float> boxes32(8 * box_firsts.size(), 0.0f);  // the same records in fp32 (fscene::boxes)
@@ -2464,6 +2473,7 @@ int upload_scene(handle_t* h, const rtw_scene_desc* d) {
         h->f32_bytes = (uint32_t)(p2[8].off + p2[8].bytes);
         F.nodes = S.nodes ? (const node_store*)(b2 + p2[9].off) : nullptr;
         F.boxes = p2[10].bytes ? (const float*)(b2 + p2[10].off) : nullptr;
+        F.texels = S.texels;
         F.items = S.items;
         F.runs = S.runs;
         F.media = S.media;
@@ -2485,14 +2495,17 @@ int upload_scene(handle_t* h, const rtw_scene_desc* d) {
 // Shade kernels are instantiated for a few material/texture sets; a scene
 // runs the smallest instantiated superset of its own set.
 constexpr int SF_NOCHECKER = SF_ALL & ~SF_CHECKER;  // the Book-2 set: noise, metal, glass, media
-constexpr int kShadeMasks[] = {SF_DIEL, SF_METAL | SF_DIEL, SF_NOISE, SF_NOCHECKER, SF_ALL};
+// Scenes with image textures (SF_IMAGE) run one set: everything.  A scene
+// without them matches one of the sets before it, as it always did.
+constexpr int SF_IMG_ALL = SF_ALL | SF_IMAGE;
+constexpr int kShadeMasks[] = {SF_DIEL, SF_METAL | SF_DIEL, SF_NOISE, SF_NOCHECKER, SF_ALL, SF_IMG_ALL};
 
 constexpr uint32_t kShadeLdsMax = 40 * 1024;
 
 int pick_shade_mask(int mask) {
     for (int cand : kShadeMasks)
         if ((mask & ~cand) == 0) return cand;
-    return SF_ALL;
+    return SF_IMG_ALL;
 }
 
 // Kernel names as rocprofv3 demangles them ("k_persist_sort<112, 8, true>"),
@@ -2515,6 +2528,22 @@ bool launch_segment(bool probe, int f, int mask, int grid, hipStream_t st, const
     const int pick = pick_shade_mask(mask);
     const bool lds = bytes <= kShadeLdsMax;
     const size_t shm = lds ? bytes : 0;
+#ifndef RTW_SUBSET
+    // image scenes: the list and the world-BVH forms, scene data through the
+    // caches; any other feature set takes the split pair (k_shade<SF_IMG_ALL>)
+#define RTW_SEG_IMG(FF)                                                                                        \
+    if ((pick & SF_IMAGE) && f == (FF)) {                                                                    \
+        if (name) *name = kname("k_segment", FF, SF_IMG_ALL, 0);                                             \
+        if (!probe)                                                                                           \
+            hipLaunchKernelGGL((k_segment<FF, SF_IMG_ALL, false>), dim3(grid), dim3(kBlock), 0, st, S, J, A, FR, C, \
+                               base, bytes);                                                                 \
+        return true;                                                                                         \
+    }
+    RTW_SEG_IMG(0)
+    RTW_SEG_IMG(F_WBVH)
+#undef RTW_SEG_IMG
+#endif
+    if (pick & SF_IMAGE) return false;
 #define RTW_SEG(FF, MM, LL)                                                                                    \
     if (f == (FF) && pick == (MM) && lds == (LL)) {                                                          \
         if (name) *name = kname("k_segment", FF, MM, LL);                                                    \
@@ -2671,8 +2700,26 @@ bool launch_persist(bool probe, int f, int mask, int cus, hipStream_t st, const 
                     const char* base, uint32_t bytes, int stack_need = kStack, bool ysph = false,
                     bool static_scene = false, bool lights = false, bool black = false, bool pin = false,
                     std::string* name = nullptr) {
-    if (ysph && !(f & (F_WBVH | F_MEDIA))) f |= F_YSPH;  // world runs are walked: y-sphere scans
     const int pick = pick_shade_mask(mask);
+    if (pick & SF_IMAGE) {
+        // Scenes with image textures: one persistent instantiation for list
+        // scenes (y-sphere runs take group_scan: same results) and one for a
+        // world BVH, every material and texture, scene data through the
+        // caches.  Any other feature set (media, group BVHs) has no persistent
+        // form and falls back to the wavefront kernels, which cover it.
+#ifndef RTW_SUBSET
+        if (f == 0) {
+            launch_pk<0, SF_IMG_ALL, false>(probe, name, cus, 0, st, S, J, C, base, bytes, stack_need);
+            return true;
+        }
+        if (f == F_WBVH) {
+            launch_pk<F_WBVH, SF_IMG_ALL, false>(probe, name, cus, 0, st, S, J, C, base, bytes, stack_need);
+            return true;
+        }
+#endif
+        return false;
+    }
+    if (ysph && !(f & (F_WBVH | F_MEDIA))) f |= F_YSPH;  // world runs are walked: y-sphere scans
     // specialised kernels only
     const int fs = f | (static_scene ? F_STATIC : 0) | (lights ? F_LIGHTS : F_NOLIGHTS) | (black ? F_BLACK : 0);
     const bool lds = bytes <= kShadeLdsMax;
@@ -2804,8 +2851,26 @@ bool fast_sort_enabled() {
 }
 // the stack a persistent fp64 launch with LDS stacks needs
 int lst_stack_need(const handle_t* h) { return h->stack_need; }
+// fp32 renders of a scene with image textures exist for list and world-BVH
+// scenes (launch_fast); media or group BVHs with images: fp64 only.
+bool fast_image_ok(const handle_t* h) {
+    const int f = h->features & (F_MEDIA | F_WBVH | F_GBVH);
+    return !(h->shade_mask & SF_IMAGE) || f == 0 || f == F_WBVH;
+}
 void launch_fast(bool probe, const handle_t* h, hipStream_t st, const fast_args& A, std::string* name = nullptr) {
     const int f = h->features & (F_MEDIA | F_WBVH | F_GBVH);
+#ifndef RTW_SUBSET_FAST
+    if (h->shade_mask & SF_IMAGE) {
+        // scenes with image textures: k_fast with the lookup compiled in, for
+        // list scenes and world-BVH scenes (fast_image_ok: others are refused
+        // before any launch)
+        const bool lst = f == F_WBVH && h->stack_need <= rtwf::fast_stack(f) && h->S.n_nodes < 65536;
+        if (f == 0) launch_fast_t<FF_IMAGE, false>(probe, name, h->cus, st, A);
+        else if (lst) launch_fast_t<F_WBVH | FF_IMAGE, true>(probe, name, h->cus, st, A);
+        else launch_fast_t<F_WBVH | FF_IMAGE, false>(probe, name, h->cus, st, A);
+        return;
+    }
+#endif
 #ifdef RTW_SUBSET_FAST  // experiment builds (scripts/ru_kernel.sh): the list scenes' fp32 kernel only
 #ifdef RTW_SUBSET_FAST_F  // ... or one BVH kernel k_fast<RTW_SUBSET_FAST_F, true>
     launch_fast_t<RTW_SUBSET_FAST_F, true>(probe, name, h->cus, st, A);
@@ -2875,6 +2940,11 @@ void launch_shade(int mask, int grid, hipStream_t st, const scene& S, const job_
         RTW_CASE(SF_NOISE, true)
         RTW_CASE(SF_NOISE, false)
         RTW_CASE(SF_ALL, true)
+        RTW_CASE(SF_IMG_ALL, false)
+        case SF_IMG_ALL * 2 + 1:  // (no LDS form for image scenes)
+            hipLaunchKernelGGL((k_shade<SF_IMG_ALL, false>), dim3(grid), dim3(kBlock), 0, st, S, J, A, F, ht, hid, C, base,
+                               bytes);
+            break;
 #endif
 #undef RTW_CASE
     default:
@@ -3175,6 +3245,9 @@ extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera
                                                  h->S.render_type != RTW_RENDER_NORMAL,
                                              pin));
     }
+    if (fast && !fast_image_ok(h))
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "precision fp32 with image textures covers list and world-BVH scenes only "
+                                             "(this scene has media or group BVHs): render it in fp64");
     if (RTW_STRICT_RADIANCE && !persistent)
         return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders with the persistent kernel only "
                                              "(RTW_MODE=wavefront or a scene without a persistent instantiation)");

@@ -5,7 +5,10 @@
 //
 //   rtw_render [--scene cornell_box] [--nx 400] [--ny 400] [--spp 64]
 //              [--depth 100] [--seed 0] [--bvh] [--device 0] [--gpus 1]
-//              [--precision fp64|fp32] [--out out.ppm]
+//              [--precision fp64|fp32] [--out out.ppm] [--image FILE.ppm]
+//
+// --image FILE.ppm (with --scene textured): a P6 or P3 PPM, maxval 255, that
+// replaces the scene's first image texture (rtw_load_ppm).
 //
 // --precision fp64 (default) is the parity mode (the reference's double
 // arithmetic on every path decision); fp32 the fast mode (single precision,
@@ -26,7 +29,7 @@
 #include "rtw_gpu.h"
 
 int main(int argc, char** argv) {
-    std::string scene_name = "cornell_box", out = "1.ppm";
+    std::string scene_name = "cornell_box", out = "1.ppm", image;
     int nx = 400, ny = 400, spp = 64, depth = 100, device = 0, bvh = 0, gpus = 1, precision = RTW_PRECISION_FP64;
     unsigned long long seed = 0;
     for (int i = 1; i < argc; ++i) {
@@ -48,6 +51,7 @@ int main(int argc, char** argv) {
         else if (a == "--gpus") gpus = std::atoi(next());
         else if (a == "--out") out = next();
         else if (a == "--bvh") bvh = 1;
+        else if (a == "--image") image = next();
         else if (a == "--precision") {
             const std::string v = next();
             if (v == "fp64") precision = RTW_PRECISION_FP64;
@@ -63,7 +67,22 @@ int main(int argc, char** argv) {
         }
     }
 
-    auto sc = make_builtin_scene(scene_name, nx * 1.0 / ny);  // RayTracingWeekend.cpp:204
+    std::unique_ptr<scene> sc;
+    if (!image.empty()) {
+        if (scene_name != "textured") {
+            std::fprintf(stderr, "--image needs --scene textured\n");
+            return 2;
+        }
+        auto pixels = std::make_shared<image_texture::byte_array>();
+        int inx = 0, iny = 0;
+        if (rtw_load_ppm(image, *pixels, inx, iny) != RTW_OK) {
+            std::fprintf(stderr, "image: %s\n", rtw_last_error());
+            return 1;
+        }
+        sc = std::make_unique<textured_scene>(nx * 1.0 / ny, pixels, inx, iny);
+    } else {
+        sc = make_builtin_scene(scene_name, nx * 1.0 / ny);  // RayTracingWeekend.cpp:204
+    }
     if (!sc) {
         std::fprintf(stderr, "unknown scene %s\n", scene_name.c_str());
         return 2;
