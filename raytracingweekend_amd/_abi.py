@@ -135,6 +135,29 @@ SIGNATURES = {
     "rtw_write_ppm_quantized": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
 }
 
+
+
+class rtw_noise_summary(C.Structure):
+    """include/rtw_noise.h"""
+    _fields_ = [("pixels", C.c_uint64), ("nonfinite", C.c_uint64), ("mean_rel", C.c_double),
+                ("max_rel", C.c_double), ("rms_stderr", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# the functions of include/rtw_noise.h (an addition to the ABI above: its own
+# header, its own table)
+NOISE_SIGNATURES = {
+    "rtw_render_accumulate_moments": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera_desc),
+                                                C.POINTER(rtw_render_params), C.c_void_p, C.c_void_p,
+                                                C.POINTER(rtw_stats)]),
+    "rtw_noise_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                     C.POINTER(rtw_noise_summary)]),
+    "rtw_noise_estimate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_double, C.c_void_p, C.POINTER(rtw_noise_summary)]),
+}
+
 _lib = None
 
 
@@ -155,7 +178,7 @@ def load_library(path) -> C.CDLL:
         raise RuntimeError(f"native library {path} is missing: build it with "
                            f"`python -m raytracingweekend_amd.build` (there is no CPU fallback)")
     L = C.CDLL(str(path))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in [*SIGNATURES.items(), *NOISE_SIGNATURES.items()]:
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

@@ -41,11 +41,12 @@ DEVICE = [f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
 HOST_SOURCES = sorted((CSRC / "host").glob("*.cpp"))
 DEVICE_SOURCES = sorted(CSRC.glob("*.hip"))
-HEADERS = sorted(list(CSRC.rglob("*.h")) + [ROOT / "include" / "rtw_gpu.h"])
+PUBLIC_HEADERS = [ROOT / "include" / "rtw_gpu.h", ROOT / "include" / "rtw_noise.h"]
+HEADERS = sorted(list(CSRC.rglob("*.h")) + PUBLIC_HEADERS)
 # what the device sources include: the build id and the kernels' rebuilds
 # follow these only (the host scene API headers under csrc/host/rtw/ do not
 # reach the kernels)
-DEVICE_HEADERS = sorted([*CSRC.glob("rtw_*.h"), CSRC / "host" / "rtw_host_util.h", ROOT / "include" / "rtw_gpu.h"])
+DEVICE_HEADERS = sorted([*CSRC.glob("rtw_*.h"), CSRC / "host" / "rtw_host_util.h", *PUBLIC_HEADERS])
 # RCCL for rtw_render_multi (multi.cpp); the same librccl.so.1 torch loads
 LIBS = ["-L/opt/rocm/lib", "-lrccl"]
 

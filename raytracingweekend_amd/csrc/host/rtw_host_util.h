@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "rtw_gpu.h"
+#include "rtw_noise.h"
 
 // Record `msg` as this thread's last error and return `code`.
 int rtw_fail(int code, const std::string& msg);
@@ -34,3 +35,12 @@ int rtw_handle_add_device(void* handle, double* dst, const double* src, size_t n
 // rtw_render_multi over one GPU); rtw_render_multi over several GPUs refuses
 // it (RTW_ERR_UNSUPPORTED) until a multi-GPU run covers the cross-device write.
 int rtw_check_device_ptr(const void* p, int device, const char* what, bool allow_managed = true);
+
+// rtw_noise.h's shared pieces (noise.cpp), used by the device estimator too:
+// the argument checks of rtw_noise_estimate[_device], whether two buffers of
+// `bytes` bytes share a byte, and the summary from the image-wide sums.
+bool rtw_ranges_overlap(const void* a, const void* b, size_t bytes);
+int rtw_noise_check_args(const char* what, const void* accum, const void* accum_sq, int nx, int ny, int n,
+                         double floor, const void* stderr_rgb);
+void rtw_noise_finish(uint64_t pixels, uint64_t nonfinite, double sum_rel, double max_rel, double sum_se2,
+                      rtw_noise_summary* out);

@@ -19,6 +19,7 @@
 //     k_compact    (tail only, once the sample queue is drained) stream
 //                  compaction of live paths, __ballot/prefix-sum per tile
 //   k_reduce     per-pixel sum of the samples in increasing sample order
+//                (k_reduce_moments: and of their squares, rtw_noise.h)
 //
 // Paths are independent (the RNG is keyed by (seed, pixel, sample)), so the
 // pool order never changes a result, only its speed.
@@ -1731,6 +1732,44 @@ __global__ __launch_bounds__(kBlock) void k_reduce(const T* __restrict__ L, uint
         run[3 * p] = r, run[3 * p + 1] = g, run[3 * p + 2] = bl;
     }
 }
+// k_reduce, and in the same read of each record run2[pix] += x*x (one rounded
+// product, one rounded add: the library builds with -ffp-contract=off), the
+// raw second moment of rtw_noise.h.  Same access pattern as k_reduce (a wave
+// reads 64 consecutive records of one sample plane); the records of kAhead
+// samples are loaded before the first of them is added, the additions stay
+// in sample order.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_reduce_moments(const T* __restrict__ L, uint32_t npix, uint32_t spp,
+                                                           double* __restrict__ run, double* __restrict__ run2) {
+    constexpr uint32_t kAhead = 4;
+    for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < npix; p += gridDim.x * kBlock) {
+        double r = run[3 * p], g = run[3 * p + 1], bl = run[3 * p + 2];
+        double r2 = run2[3 * p], g2 = run2[3 * p + 1], bl2 = run2[3 * p + 2];
+        uint32_t s = 0;
+        for (; s + kAhead <= spp; s += kAhead) {
+            T x[kAhead][3];
+#pragma unroll
+            for (uint32_t k = 0; k < kAhead; ++k) {
+                const T* src = L + 3 * ((size_t)(s + k) * npix + p);
+                x[k][0] = src[0], x[k][1] = src[1], x[k][2] = src[2];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kAhead; ++k) {
+                const double xr = (double)x[k][0], xg = (double)x[k][1], xb = (double)x[k][2];
+                r = r + xr, g = g + xg, bl = bl + xb;
+                r2 = r2 + xr * xr, g2 = g2 + xg * xg, bl2 = bl2 + xb * xb;
+            }
+        }
+        for (; s < spp; ++s) {
+            const T* src = L + 3 * ((size_t)s * npix + p);
+            const double xr = (double)src[0], xg = (double)src[1], xb = (double)src[2];
+            r = r + xr, g = g + xg, bl = bl + xb;
+            r2 = r2 + xr * xr, g2 = g2 + xg * xg, bl2 = bl2 + xb * xb;
+        }
+        run[3 * p] = r, run[3 * p + 1] = g, run[3 * p + 2] = bl;
+        run2[3 * p] = r2, run2[3 * p + 1] = g2, run2[3 * p + 2] = bl2;
+    }
+}
 // k_reduce's grid for npix pixels
 unsigned reduce_grid(uint64_t npix) {
     return (unsigned)std::min<uint64_t>((npix + kBlock - 1) / kBlock, 4096);
@@ -1754,6 +1793,84 @@ __global__ __launch_bounds__(kBlock) void k_finalize(const double* __restrict__ 
     for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
         const double s = __builtin_sqrt(accum[k] / spp);
         canvas[k] = (1.0 < s) ? 1.0 : s;
+    }
+}
+
+// rtw_noise.h on the device: the standard error of every channel from the
+// raw moments (the operations of rtw_noise_estimate, noise.cpp, in the same
+// order: the map is bit-identical) and one partial of the image-wide summary
+// per block.  Deterministic: a thread takes pixels p, p + grid*kBlock, ... in
+// order, a wave folds its lanes with a fixed shuffle tree, thread 0 adds the
+// waves' values from LDS in wave order, the host adds the blocks' partials in
+// block order; the grid (noise_grid) depends on the pixel count only.  No
+// atomics: the two counters travel in the partials as well.
+struct noise_part {
+    double sum_rel, max_rel, sum_se2;
+    unsigned long long pixels, nonfinite;
+};
+constexpr unsigned kNoiseMaxGrid = 1024;
+unsigned noise_grid(uint64_t npix) {
+    return (unsigned)std::min<uint64_t>((npix + kBlock - 1) / kBlock, kNoiseMaxGrid);
+}
+
+__global__ __launch_bounds__(kBlock) void k_noise_pixels(const double* __restrict__ accum,
+                                                         const double* __restrict__ accum_sq, uint64_t npix,
+                                                         double dn, double dn1, double floor3,
+                                                         double* __restrict__ stderr_rgb,
+                                                         noise_part* __restrict__ parts) {
+    __shared__ noise_part s_part[kWaves];
+    noise_part a;
+    a.sum_rel = 0.0, a.max_rel = -__builtin_inf(), a.sum_se2 = 0.0, a.pixels = 0, a.nonfinite = 0;
+    // (64-bit p: the stride may carry p past 2^32 for the largest images)
+    for (uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x; p < npix; p += (uint64_t)gridDim.x * kBlock) {
+        double se[3], m[3];
+        bool finite = true;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double s1 = accum[3 * p + c], s2 = accum_sq[3 * p + c];
+            finite = finite && __builtin_isfinite(s1) && __builtin_isfinite(s2);
+            m[c] = s1 / dn;
+            double v = (s2 - s1 * m[c]) / dn1;
+            if (v < 0.0) v = 0.0;
+            se[c] = __builtin_sqrt(v / dn);
+        }
+        if (!finite) {
+            ++a.nonfinite;
+            if (stderr_rgb) {
+                const double nan = __builtin_nan("");
+                stderr_rgb[3 * p] = nan, stderr_rgb[3 * p + 1] = nan, stderr_rgb[3 * p + 2] = nan;
+            }
+            continue;
+        }
+        if (stderr_rgb) stderr_rgb[3 * p] = se[0], stderr_rgb[3 * p + 1] = se[1], stderr_rgb[3 * p + 2] = se[2];
+        const double rel = ((se[0] + se[1]) + se[2]) / (((m[0] + m[1]) + m[2]) + floor3);
+        ++a.pixels;
+        a.sum_rel = a.sum_rel + rel;
+        if (rel > a.max_rel) a.max_rel = rel;
+        a.sum_se2 = a.sum_se2 + ((se[0] * se[0] + se[1] * se[1]) + se[2] * se[2]);
+    }
+    // (all 256 threads reach here: the loop above has no barrier)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a.sum_rel = a.sum_rel + __shfl_down(a.sum_rel, off, 64);
+        a.sum_se2 = a.sum_se2 + __shfl_down(a.sum_se2, off, 64);
+        const double mx = __shfl_down(a.max_rel, off, 64);
+        if (mx > a.max_rel) a.max_rel = mx;
+        a.pixels += __shfl_down(a.pixels, off, 64);
+        a.nonfinite += __shfl_down(a.nonfinite, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        noise_part t = s_part[0];
+        for (int w = 1; w < kWaves; ++w) {
+            t.sum_rel = t.sum_rel + s_part[w].sum_rel;
+            t.sum_se2 = t.sum_se2 + s_part[w].sum_se2;
+            if (s_part[w].max_rel > t.max_rel) t.max_rel = s_part[w].max_rel;
+            t.pixels += s_part[w].pixels;
+            t.nonfinite += s_part[w].nonfinite;
+        }
+        parts[blockIdx.x] = t;
     }
 }
 
@@ -1816,6 +1933,9 @@ struct handle_t {
     dev_buf run;      // per-pixel running sums
     dev_buf flog;     // RTW_STRICT_RADIANCE: per-thread factor logs (job_t::flog)
     dev_buf accum;    // device accum when the caller passes a host pointer
+    dev_buf run2;     // rtw_render_accumulate_moments: per-pixel running sums of squares
+    dev_buf accum_sq; // ... device accum_sq when the caller passes a host pointer
+    dev_buf noise;    // rtw_noise_estimate_device: per-block partials (noise_part)
     dev_buf ctrs;
     dev_buf camera;                // device copy of the call's camera
     rtw_camera_desc cam_host{};    // its source (lives until the copy ran)
@@ -3166,6 +3286,9 @@ extern "C" void rtw_scene_free(void* handle) {
     h->run.release();
     h->flog.release();
     h->accum.release();
+    h->run2.release();
+    h->accum_sq.release();
+    h->noise.release();
     h->ctrs.release();
     h->camera.release();
     if (h->host_ctrs) hipHostFree(h->host_ctrs);
@@ -3188,10 +3311,13 @@ extern "C" int rtw_finalize_canvas_device(void* handle, const double* accum, int
     return RTW_OK;
 }
 
-extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
-                                     double* accum_rgb, rtw_stats* out_stats) {
-    handle_t* h = static_cast<handle_t*>(handle);
-    if (!h || !camera || !prm || !accum_rgb) return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate: null argument");
+// The render of rtw_render_accumulate and, with accum_sq set, of
+// rtw_render_accumulate_moments (rtw_noise.h): the same launches, allocations
+// and copies, except that k_reduce_moments takes k_reduce's place and a
+// second k_emit adds the sums of squares.  With accum_sq null nothing here
+// differs from the plain render.
+static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                             double* accum_rgb, double* accum_sq, rtw_stats* out_stats) {
     const rtw_render_params& R = *prm;
     if (R.nx <= 0 || R.ny <= 0 || R.spp <= 0 || R.spp_begin < 0 || R.spp_begin > R.spp || R.spp_count < 0)
         return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate: bad image / sample parameters");
@@ -3210,9 +3336,14 @@ extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera
         return rtw_fail(RTW_ERR_INVALID,
                         "rtw_render_accumulate: camera shutter outside the one the scene's BVH was built for "
                         "(moving spheres); flatten the scene with this camera");
+    if (accum_sq && rtw_ranges_overlap(accum_rgb, accum_sq, (size_t)R.nx * R.ny * 24))
+        return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_moments: accum_rgb and accum_sq_rgb overlap");
     HIPCHK(hipSetDevice(h->device));
-    if (R.accum_on_device)
+    if (R.accum_on_device) {
         if (int rc = rtw_check_device_ptr(accum_rgb, h->device, "rtw_render_accumulate")) return rc;
+        if (accum_sq)
+            if (int rc = rtw_check_device_ptr(accum_sq, h->device, "rtw_render_accumulate_moments")) return rc;
+    }
     hipStream_t st = h->stream;
 
     rtw_stats stats;
@@ -3268,14 +3399,30 @@ extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera
     if ((rc = h->hits.ensure((size_t)pool * 12))) return rc;
     if ((rc = h->radiance.ensure(pass_samples * 24))) return rc;
     if ((rc = h->run.ensure(npix * 24))) return rc;
+    if (accum_sq && (rc = h->run2.ensure(npix * 24))) return rc;
     paths_t A = carve_paths(h->pool[0].p, pool), B = carve_paths(h->pool[1].p, pool);
     const fresh_t FR = carve_fresh(h->fresh.p, pool);
     double* ht = static_cast<double*>(h->hits.p);
     int32_t* hid = reinterpret_cast<int32_t*>(static_cast<char*>(h->hits.p) + (size_t)pool * 8);
     ctrs_t* C = static_cast<ctrs_t*>(h->ctrs.p);
     double* run = static_cast<double*>(h->run.p);
+    double* run2 = accum_sq ? static_cast<double*>(h->run2.p) : nullptr;
     HIPCHK(hipMemsetAsync(run, 0, npix * 24, st));
+    if (run2) HIPCHK(hipMemsetAsync(run2, 0, npix * 24, st));
     HIPCHK(hipMemsetAsync(C, 0, sizeof(ctrs_t), st));
+    // the ordered per-pixel reduction of one pass's records (k_reduce, or with
+    // accum_sq k_reduce_moments: both sums from one read of each record)
+    auto launch_reduce = [&](bool f32, const double* L, uint32_t S_pass) {
+        const dim3 g(reduce_grid(npix)), b(kBlock);
+        const float* Lf = reinterpret_cast<const float*>(L);
+        if (run2) {
+            if (f32) hipLaunchKernelGGL(k_reduce_moments<float>, g, b, 0, st, Lf, (uint32_t)npix, S_pass, run, run2);
+            else hipLaunchKernelGGL(k_reduce_moments<double>, g, b, 0, st, L, (uint32_t)npix, S_pass, run, run2);
+        } else {
+            if (f32) hipLaunchKernelGGL(k_reduce<float>, g, b, 0, st, Lf, (uint32_t)npix, S_pass, run);
+            else hipLaunchKernelGGL(k_reduce<double>, g, b, 0, st, L, (uint32_t)npix, S_pass, run);
+        }
+    };
 
     job_t J;
     h->cam_host = *camera;
@@ -3373,12 +3520,7 @@ extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera
             }
             stats.launches_intersect++;
             stats.iterations++;
-            if (fast)
-                hipLaunchKernelGGL(k_reduce<float>, dim3(reduce_grid(npix)), dim3(kBlock), 0, st,
-                                   reinterpret_cast<const float*>(J.L), (uint32_t)npix, S_pass, run);
-            else
-                hipLaunchKernelGGL(k_reduce<double>, dim3(reduce_grid(npix)), dim3(kBlock), 0, st, J.L,
-                                   (uint32_t)npix, S_pass, run);
+            launch_reduce(fast, J.L, S_pass);
             HIPCHK(hipGetLastError());
             stats.samples += J.total;
             continue;
@@ -3457,8 +3599,7 @@ extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera
                 if (tail && snap.n == 0) break;
             }
         }
-        hipLaunchKernelGGL(k_reduce<double>, dim3(reduce_grid(npix)), dim3(kBlock), 0, st,
-                           J.L, (uint32_t)npix, S_pass, run);  // the wavefront form is fp64 only
+        launch_reduce(false, J.L, S_pass);  // the wavefront form is fp64 only
         HIPCHK(hipGetLastError());
         stats.samples += J.total;
     }
@@ -3475,6 +3616,18 @@ extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera
                        (uint32_t)npix, R.nx, R.row_begin, row_step, acc_dev);
     HIPCHK(hipGetLastError());
     if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(accum_rgb, acc_dev, img_bytes, hipMemcpyDeviceToHost, st));
+    if (accum_sq) {  // accum_sq += run2, the same way
+        double* sq_dev = accum_sq;
+        if (!R.accum_on_device) {
+            if ((rc = h->accum_sq.ensure(img_bytes))) return rc;
+            sq_dev = static_cast<double*>(h->accum_sq.p);
+            HIPCHK(hipMemcpyAsync(sq_dev, accum_sq, img_bytes, hipMemcpyHostToDevice, st));
+        }
+        hipLaunchKernelGGL(k_emit, dim3(std::min<uint64_t>((npix + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st,
+                           run2, (uint32_t)npix, R.nx, R.row_begin, row_step, sq_dev);
+        HIPCHK(hipGetLastError());
+        if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(accum_sq, sq_dev, img_bytes, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipMemcpyAsync(&h->host_ctrs[63], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(ev_end, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -3542,5 +3695,56 @@ extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera
     // (fp32 fast mode: 7 x 4 B ray in, 4 + 4 B hit out = 36 B)
     stats.bytes_intersect = (fast ? 36.0 : 68.0) * (double)stats.segments;
     if (out_stats) *out_stats = stats;
+    return RTW_OK;
+}
+
+extern "C" int rtw_render_accumulate(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                                     double* accum_rgb, rtw_stats* out_stats) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    if (!h || !camera || !prm || !accum_rgb) return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate: null argument");
+    return render_accumulate(h, camera, prm, accum_rgb, nullptr, out_stats);
+}
+
+extern "C" int rtw_render_accumulate_moments(void* handle, const rtw_camera_desc* camera,
+                                             const rtw_render_params* prm, double* accum_rgb, double* accum_sq_rgb,
+                                             rtw_stats* out_stats) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    if (!h || !camera || !prm || !accum_rgb || !accum_sq_rgb)
+        return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_moments: null argument");
+    return render_accumulate(h, camera, prm, accum_rgb, accum_sq_rgb, out_stats);
+}
+
+extern "C" int rtw_noise_estimate_device(void* handle, const double* accum, const double* accum_sq, int nx, int ny,
+                                         int n, double floor, double* stderr_dev, rtw_noise_summary* out) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    if (!h) return rtw_fail(RTW_ERR_INVALID, "rtw_noise_estimate_device: null scene handle");
+    if (int rc = rtw_noise_check_args("rtw_noise_estimate_device", accum, accum_sq, nx, ny, n, floor, stderr_dev))
+        return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = rtw_check_device_ptr(accum, h->device, "rtw_noise_estimate_device")) return rc;
+    if (int rc = rtw_check_device_ptr(accum_sq, h->device, "rtw_noise_estimate_device")) return rc;
+    if (stderr_dev)
+        if (int rc = rtw_check_device_ptr(stderr_dev, h->device, "rtw_noise_estimate_device")) return rc;
+    const uint64_t npix = (uint64_t)nx * (uint64_t)ny;
+    const unsigned grid = noise_grid(npix);
+    if (int rc = h->noise.ensure(sizeof(noise_part) * kNoiseMaxGrid)) return rc;
+    noise_part* parts = static_cast<noise_part*>(h->noise.p);
+    hipLaunchKernelGGL(k_noise_pixels, dim3(grid), dim3(kBlock), 0, h->stream, accum, accum_sq, npix, (double)n,
+                       (double)(n - 1), 3.0 * floor, stderr_dev, parts);
+    HIPCHK(hipGetLastError());
+    std::vector<noise_part> host(grid);
+    HIPCHK(hipMemcpyAsync(host.data(), parts, sizeof(noise_part) * grid, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (out) {
+        noise_part t = host[0];  // the blocks' partials, in block order
+        for (unsigned b = 1; b < grid; ++b) {
+            t.sum_rel = t.sum_rel + host[b].sum_rel;
+            t.sum_se2 = t.sum_se2 + host[b].sum_se2;
+            if (host[b].max_rel > t.max_rel) t.max_rel = host[b].max_rel;
+            t.pixels += host[b].pixels;
+            t.nonfinite += host[b].nonfinite;
+        }
+        rtw_noise_finish(t.pixels, t.nonfinite, t.sum_rel, t.max_rel, t.sum_se2, out);
+    }
     return RTW_OK;
 }

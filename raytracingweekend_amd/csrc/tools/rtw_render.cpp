@@ -6,6 +6,13 @@
 //   rtw_render [--scene cornell_box] [--nx 400] [--ny 400] [--spp 64]
 //              [--depth 100] [--seed 0] [--bvh] [--device 0] [--gpus 1]
 //              [--precision fp64|fp32] [--out out.ppm] [--image FILE.ppm]
+//              [--noise] [--noise-target X [--noise-batch 8] [--noise-floor 0.01]]
+//
+// --noise renders through rtw_render_accumulate_moments (rtw_noise.h) and
+// prints the image-wide noise estimate of the --spp samples.  --noise-target X
+// renders the sample ranges [0,b) [b,2b) [2b,4b) ... (b = --noise-batch) until
+// the estimate's mean relative standard error is at most X or --spp samples
+// are done, and finalizes the canvas with the samples it used.  One GPU only.
 //
 // --image FILE.ppm (with --scene textured): a P6 or P3 PPM, maxval 255, that
 // replaces the scene's first image texture (rtw_load_ppm).
@@ -27,11 +34,15 @@
 #include <vector>
 #include "rtw/scene.h"
 #include "rtw_gpu.h"
+#include "rtw_noise.h"
 
 int main(int argc, char** argv) {
     std::string scene_name = "cornell_box", out = "1.ppm", image;
     int nx = 400, ny = 400, spp = 64, depth = 100, device = 0, bvh = 0, gpus = 1, precision = RTW_PRECISION_FP64;
     unsigned long long seed = 0;
+    bool noise = false, to_target = false;
+    double noise_target = 0.0, noise_floor = 1e-2;
+    int noise_batch = 8;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -52,6 +63,10 @@ int main(int argc, char** argv) {
         else if (a == "--out") out = next();
         else if (a == "--bvh") bvh = 1;
         else if (a == "--image") image = next();
+        else if (a == "--noise") noise = true;
+        else if (a == "--noise-target") noise_target = std::atof(next()), noise = to_target = true;
+        else if (a == "--noise-batch") noise_batch = std::atoi(next());
+        else if (a == "--noise-floor") noise_floor = std::atof(next());
         else if (a == "--precision") {
             const std::string v = next();
             if (v == "fp64") precision = RTW_PRECISION_FP64;
@@ -65,6 +80,15 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
         }
+    }
+
+    if (noise && gpus != 1) {
+        std::fprintf(stderr, "--noise / --noise-target render on one GPU (--gpus 1)\n");
+        return 2;
+    }
+    if (noise && (spp < 2 || noise_batch < 2 || (to_target && !(noise_target > 0.0)) || !(noise_floor > 0.0))) {
+        std::fprintf(stderr, "--noise needs --spp >= 2, --noise-batch >= 2, --noise-target > 0, --noise-floor > 0\n");
+        return 2;
     }
 
     std::unique_ptr<scene> sc;
@@ -109,14 +133,43 @@ int main(int argc, char** argv) {
     p.precision = precision;
     std::vector<double> accum((size_t)nx * ny * 3, 0.0), canvas(accum.size());
     rtw_stats st;
+    std::memset(&st, 0, sizeof st);
+    int spp_done = spp;
+    rtw_noise_summary ns;
+    std::memset(&ns, 0, sizeof ns);
     auto t0 = std::chrono::high_resolution_clock::now();
-    const int rc = gpus == 1 ? rtw_render_accumulate(h[0], &cam, &p, accum.data(), &st)
-                             : rtw_render_multi(gpus, h.data(), &cam, &p, accum.data(), &st);
-    if (rc != RTW_OK) {
-        std::fprintf(stderr, "render: %s\n", rtw_last_error());
-        return 1;
+    if (noise) {
+        // one batch of all samples, or (--noise-target) batches that double the
+        // total until the estimate reaches the target (render.render_to_noise)
+        std::vector<double> accum_sq(accum.size(), 0.0);
+        spp_done = 0;
+        while (spp_done < spp) {
+            const int want = to_target ? (spp_done == 0 ? noise_batch : spp_done) : spp;
+            p.spp_begin = spp_done;
+            p.spp_count = want < spp - spp_done ? want : spp - spp_done;
+            rtw_stats sb;
+            if (rtw_render_accumulate_moments(h[0], &cam, &p, accum.data(), accum_sq.data(), &sb) != RTW_OK) {
+                std::fprintf(stderr, "render: %s\n", rtw_last_error());
+                return 1;
+            }
+            st.samples += sb.samples, st.segments += sb.segments;
+            spp_done += p.spp_count;
+            if (rtw_noise_estimate(accum.data(), accum_sq.data(), nx, ny, spp_done, noise_floor, nullptr, &ns) !=
+                RTW_OK) {
+                std::fprintf(stderr, "noise: %s\n", rtw_last_error());
+                return 1;
+            }
+            if (to_target && ns.mean_rel <= noise_target) break;
+        }
+    } else {
+        const int rc = gpus == 1 ? rtw_render_accumulate(h[0], &cam, &p, accum.data(), &st)
+                                 : rtw_render_multi(gpus, h.data(), &cam, &p, accum.data(), &st);
+        if (rc != RTW_OK) {
+            std::fprintf(stderr, "render: %s\n", rtw_last_error());
+            return 1;
+        }
     }
-    rtw_finalize_canvas(accum.data(), nx, ny, spp, canvas.data());
+    rtw_finalize_canvas(accum.data(), nx, ny, spp_done, canvas.data());
     auto t1 = std::chrono::high_resolution_clock::now();
     if (rtw_write_ppm(out.c_str(), canvas.data(), nx, ny) != RTW_OK) {
         std::fprintf(stderr, "write: %s\n", rtw_last_error());
@@ -129,6 +182,9 @@ int main(int argc, char** argv) {
     std::printf("Msamples/s: %.3f  segments/sample: %.4f\n",
                 (double)st.samples / (std::chrono::duration<double>(t1 - t0).count() * 1e6),
                 (double)st.segments / (double)st.samples);
+    if (noise)
+        std::printf("Noise: spp %d of %d  mean_rel %.6e  max_rel %.6e  rms_stderr %.6e\n", spp_done, spp,
+                    ns.mean_rel, ns.max_rel, ns.rms_stderr);
     for (void* x : h) rtw_scene_free(x);
     if (gpus > 1) rtw_release_communicators();
     rtw_scene_desc_free(desc);

@@ -18,6 +18,13 @@ Two shardings:
 tests/test_distributed.py (gloo ranks on the CPU, the oracle standing in for
 each rank's renderer) run.  A C/C++ host without torch uses rtw_render_multi
 (include/rtw_gpu.h) instead: one process, one thread per GPU, RCCL inside.
+
+Noise estimate (include/rtw_noise.h): DeviceScene.render_moments keeps RAW
+second moments (per-pixel sums of squares), which are additive across sample
+ranges and rows exactly as the radiance sums are.  A sharded run that wants
+the estimate renders its shard with render_moments and issues a second
+dist.reduce(accum_sq, dst=0) beside the one of accum; rank 0 then calls
+noise_estimate with the total spp.  Nothing else changes.
 """
 from __future__ import annotations
 

@@ -83,20 +83,7 @@ class DeviceScene:
         (accum, stats dict)."""
         if accum is None:
             accum = np.zeros(nx * ny * 3, dtype=np.float64)
-        on_device = 0
-        if isinstance(accum, np.ndarray):
-            if accum.dtype != np.float64 or accum.size != nx * ny * 3 or not accum.flags["C_CONTIGUOUS"]:
-                raise ValueError("accum must be a contiguous float64 array of nx*ny*3")
-            ptr = accum.ctypes.data_as(C.c_void_p)
-        else:  # torch tensor on the device
-            import torch
-            if accum.dtype != torch.float64 or accum.numel() != nx * ny * 3 or not accum.is_contiguous():
-                raise ValueError("accum must be a contiguous float64 tensor of nx*ny*3")
-            if not accum.is_cuda or accum.device.index != self.device:
-                raise ValueError(f"a torch accum must live on this scene's GPU (cuda:{self.device})")
-            torch.cuda.synchronize(accum.device)
-            ptr = C.c_void_p(accum.data_ptr())
-            on_device = 1
+        ptr, on_device = self._accum_ptr(accum, nx, ny, "accum")
         prm = _abi.rtw_render_params(nx=nx, ny=ny, spp=spp, max_depth=max_depth, seed=seed, spp_begin=spp_begin,
                                      spp_count=spp_count, row_begin=row_begin, row_step=row_step,
                                      accum_on_device=on_device, collect_kernel_times=int(collect_kernel_times),
@@ -106,6 +93,75 @@ class DeviceScene:
         check(lib().rtw_render_accumulate(self.handle, C.byref(cam), C.byref(prm), ptr, C.byref(st)),
               "rtw_render_accumulate")
         return accum, st.as_dict()
+
+    def _accum_ptr(self, accum, nx: int, ny: int, name: str):
+        """(pointer, accum_on_device) of an accumulator: a float64 numpy array
+        of nx*ny*3, or a torch float64 tensor on this device (synchronized)."""
+        if isinstance(accum, np.ndarray):
+            if accum.dtype != np.float64 or accum.size != nx * ny * 3 or not accum.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{name} must be a contiguous float64 array of nx*ny*3")
+            return accum.ctypes.data_as(C.c_void_p), 0
+        import torch
+        if accum.dtype != torch.float64 or accum.numel() != nx * ny * 3 or not accum.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float64 tensor of nx*ny*3")
+        if not accum.is_cuda or accum.device.index != self.device:
+            raise ValueError(f"a torch {name} must live on this scene's GPU (cuda:{self.device})")
+        torch.cuda.synchronize(accum.device)
+        return C.c_void_p(accum.data_ptr()), 1
+
+    def render_moments(self, nx: int, ny: int, spp: int, max_depth: int, seed: int = 0, *,
+                       spp_begin: int = 0, spp_count: int = 0, row_begin: int = 0, row_step: int = 1,
+                       accum=None, accum_sq=None, camera: Optional[_abi.rtw_camera_desc] = None,
+                       collect_kernel_times: bool = False, wavefront_paths: int = 0, precision: str = "fp64"):
+        """render_accumulate, and additionally the per-pixel sums of the
+        squares of the same samples into `accum_sq` (rtw_render_accumulate_moments:
+        the raw second moments rtw_noise.h's estimate needs).  Both buffers
+        are float64 numpy arrays of nx*ny*3, or both torch float64 CUDA
+        tensors on this device; one given alone gets a zero partner of its
+        kind.  Returns (accum, accum_sq, stats dict)."""
+        if accum is None and accum_sq is None:
+            accum = np.zeros(nx * ny * 3, dtype=np.float64)
+        if accum is None:
+            accum = _zeros_like(accum_sq)
+        if accum_sq is None:
+            accum_sq = _zeros_like(accum)
+        ptr, ptr_sq, on_device = self._moment_buffers(accum, accum_sq, nx, ny)
+        prm = _abi.rtw_render_params(nx=nx, ny=ny, spp=spp, max_depth=max_depth, seed=seed, spp_begin=spp_begin,
+                                     spp_count=spp_count, row_begin=row_begin, row_step=row_step,
+                                     accum_on_device=on_device, collect_kernel_times=int(collect_kernel_times),
+                                     wavefront_paths=wavefront_paths, precision=_precision(precision))
+        st = _abi.rtw_stats()
+        cam = camera if camera is not None else self.scene.camera
+        check(lib().rtw_render_accumulate_moments(self.handle, C.byref(cam), C.byref(prm), ptr, ptr_sq,
+                                                  C.byref(st)), "rtw_render_accumulate_moments")
+        return accum, accum_sq, st.as_dict()
+
+    def _moment_buffers(self, accum, accum_sq, nx: int, ny: int):
+        """(pointer, pointer, accum_on_device) of a pair of moment buffers:
+        both numpy, or both torch on this device (a mix: ValueError)."""
+        if isinstance(accum, np.ndarray) != isinstance(accum_sq, np.ndarray):
+            raise ValueError("accum and accum_sq must both be numpy arrays or both be torch tensors on this device")
+        ptr, on_device = self._accum_ptr(accum, nx, ny, "accum")
+        ptr_sq, _ = self._accum_ptr(accum_sq, nx, ny, "accum_sq")
+        return ptr, ptr_sq, on_device
+
+    def noise_estimate(self, accum, accum_sq, nx: int, ny: int, n: int, floor: float = 1e-2,
+                       want_stderr: bool = True):
+        """The standard-error map and summary of `n` samples' raw moments
+        (rtw_noise.h).  Torch tensors on this device go through the device
+        estimator (rtw_noise_estimate_device; the map is a tensor); numpy
+        arrays fall through to the host function, render.noise_estimate.
+        Returns (stderr or None, summary dict)."""
+        if isinstance(accum, np.ndarray) and isinstance(accum_sq, np.ndarray):
+            return noise_estimate(accum, accum_sq, nx, ny, n, floor, want_stderr)
+        ptr, ptr_sq, _ = self._moment_buffers(accum, accum_sq, nx, ny)
+        import torch
+        se = torch.empty_like(accum) if want_stderr else None
+        out = _abi.rtw_noise_summary()
+        check(lib().rtw_noise_estimate_device(self.handle, ptr, ptr_sq, nx, ny, n, floor,
+                                              C.c_void_p(se.data_ptr()) if want_stderr else None, C.byref(out)),
+              "rtw_noise_estimate_device")
+        return se, out.as_dict()
 
     def finalize_device(self, accum, nx: int, ny: int, spp: int, canvas=None):
         """canvas = min(sqrt(accum / spp), 1) on the GPU (torch float64 CUDA
@@ -217,6 +273,77 @@ def finalize(accum: np.ndarray, nx: int, ny: int, spp: int) -> np.ndarray:
     out = np.empty(nx * ny * 3, dtype=np.float64)
     lib().rtw_finalize_canvas(a.ctypes.data_as(C.c_void_p), nx, ny, spp, out.ctypes.data_as(C.c_void_p))
     return out
+
+
+def _zeros_like(a):
+    if isinstance(a, np.ndarray):
+        return np.zeros_like(a)
+    import torch
+    return torch.zeros_like(a)
+
+
+def noise_estimate(accum: np.ndarray, accum_sq: np.ndarray, nx: int, ny: int, n: int, floor: float = 1e-2,
+                   want_stderr: bool = True):
+    """rtw_noise_estimate on the host: from the raw moments of `n` samples per
+    pixel (DeviceScene.render_moments) the standard error of every channel's
+    mean and the image-wide summary {pixels, nonfinite, mean_rel, max_rel,
+    rms_stderr} (include/rtw_noise.h).  Returns (stderr array or None,
+    summary dict)."""
+    a = np.ascontiguousarray(accum, dtype=np.float64)
+    q = np.ascontiguousarray(accum_sq, dtype=np.float64)
+    if a.size != nx * ny * 3 or q.size != nx * ny * 3:
+        raise ValueError("accum and accum_sq must hold nx*ny*3 values")
+    se = np.empty(nx * ny * 3, dtype=np.float64) if want_stderr else None
+    out = _abi.rtw_noise_summary()
+    check(lib().rtw_noise_estimate(a.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), nx, ny, n, floor,
+                                   se.ctypes.data_as(C.c_void_p) if want_stderr else None, C.byref(out)),
+          "rtw_noise_estimate")
+    return se, out.as_dict()
+
+
+def render_to_noise(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: int = 0, *, target: float,
+                    first_batch: int = 8, floor: float = 1e-2, precision: str = "fp64",
+                    device_buffers: bool = False, camera=None) -> dict:
+    """Render batches of samples until the image-wide noise estimate reaches
+    `target`: the sample ranges [0,b) [b,2b) [2b,4b) ... (b = first_batch; the
+    total doubles at every check, the last batch is cut at max_spp), each
+    through ds.render_moments with spp = max_spp, and after each
+    ds.noise_estimate's mean_rel.  Stops at the first check with
+    mean_rel <= target, or at max_spp.  The RNG is keyed by (seed, pixel,
+    sample), so the buffers are those of one render of [0, spp_done) (up to
+    the rounding of adding the batches' sums).
+
+    `ds` is a DeviceScene, or anything with its render_moments and
+    noise_estimate.  device_buffers keeps both moments in torch tensors on the
+    scene's GPU.  Returns a dict: accum, accum_sq, spp_done, reached, history
+    (a list of (spp, mean_rel, max_rel)) and stats (summed over the batches).
+    Finalize the canvas with spp_done."""
+    if first_batch < 2:
+        raise ValueError("first_batch must be at least 2 (a variance needs two samples)")
+    if max_spp < 2:
+        raise ValueError("max_spp must be at least 2")
+    if not target > 0:
+        raise ValueError("target must be positive")
+    if device_buffers:
+        import torch
+        accum = torch.zeros(nx * ny * 3, dtype=torch.float64, device=f"cuda:{ds.device}")
+        accum_sq = torch.zeros_like(accum)
+    else:
+        accum = np.zeros(nx * ny * 3, dtype=np.float64)
+        accum_sq = np.zeros_like(accum)
+    done, reached, history, stats = 0, False, [], {}
+    while done < max_spp and not reached:
+        count = min(first_batch if done == 0 else done, max_spp - done)
+        _, _, st = ds.render_moments(nx, ny, max_spp, max_depth, seed, spp_begin=done, spp_count=count,
+                                     accum=accum, accum_sq=accum_sq, camera=camera, precision=precision)
+        for k, v in st.items():
+            stats[k] = stats.get(k, 0) + v
+        done += count
+        _, summary = ds.noise_estimate(accum, accum_sq, nx, ny, done, floor, want_stderr=False)
+        history.append((done, summary["mean_rel"], summary["max_rel"]))
+        reached = summary["mean_rel"] <= target
+    return {"accum": accum, "accum_sq": accum_sq, "spp_done": done, "reached": reached, "history": history,
+            "stats": stats}
 
 
 def write_ppm(path: str, canvas: np.ndarray, nx: int, ny: int) -> None:
