@@ -14,6 +14,7 @@
 #include "rtw_gpu.h"
 #include "rtw_div.h"
 #include "rtw_math.h"
+#include "rtw_select.h"
 
 #define RTW_D __device__ __forceinline__
 // vector helpers also used by the host to precompute per-primitive frames
@@ -390,26 +391,7 @@ struct scene {
     const uint8_t* texels;
 };
 
-// Scene features a traversal kernel is specialised for.
-// F_YSPH: the world list holds y-sphere runs (ysphere_scan); without it such
-// runs take group_scan (same results), which keeps the prefilter's code and
-// registers out of the kernels of other scenes (Cornell).
-// F_STATIC: no moving spheres, so a ray's time is never read (sphere.h:22-25
-// is its only reader); the persistent kernels then keep no time per path
-// (the camera still draws it: the RNG sequence is the reference's).
-// F_LIGHTS: the scene has lights, so every lambertian bounce samples the
-// mixture pdf (RayTracingWeekend.cpp:112-132) and the lights-free branch is
-// compiled out.
-// F_BLACK: black background and colour rendering (RayTracingWeekend.cpp:
-// 135-159): a miss emits 0 and the normal-visualisation branch is compiled out.
-// F_NOLIGHTS: the scene has no lights, so the mixture-pdf branch of the
-// lambertian bounce is compiled out instead.
-enum : int { F_MEDIA = 1, F_WBVH = 2, F_GBVH = 4, F_YSPH = 8, F_STATIC = 16, F_LIGHTS = 32, F_BLACK = 64,
-             F_NOLIGHTS = 128,
-             // every camera ray of the render starts at the camera's origin (a
-             // pinhole camera, lens_radius 0, whose origin has no zero
-             // coordinate: origin + offset is then exactly origin, camera.h:48)
-             F_PIN = 256 };
+// (Scene features a traversal kernel is specialised for, F_*: rtw_select.h.)
 
 // Uniform scene reads.  The scene is read-only for a whole launch; reading
 // it through the constant address space lets the compiler use scalar loads
@@ -1129,7 +1111,6 @@ RTW_D bool slab32(const bvh_node32& nd, const slab_ray& s, float t0, float t1) {
 // a world-BVH leaf) share one stack above the outer walk's entries; the host
 // checks at upload that the deepest nesting fits (rtw_scene_upload).
 constexpr int kStack = 48;
-constexpr int kLdsStack = 16;  // LDS stack entries per lane
 struct local_stack {
     static constexpr int cap = kStack;
     int s[kStack];
@@ -1595,12 +1576,8 @@ RTW_D double turb(const scene& S, d3 p) {  // noise.h:74-86
     return fabs(accum);
 }
 
-// Shade-kernel specialisation by the scene's material / texture set.
-// SF_ALL: every material and every texture but the image texture (its value
-// is part of the kernels' names); SF_IMAGE: the scene holds image textures,
-// so shading forms surface coordinates (u, v) where a texture walk reaches
-// one -- only kernels compiled with this bit carry that code.
-enum : int { SF_NOISE = 1, SF_CHECKER = 2, SF_METAL = 4, SF_DIEL = 8, SF_ISO = 16, SF_ALL = 31, SF_IMAGE = 32 };
+// (Shade-kernel specialisation by the scene's material / texture set, SF_*:
+// rtw_select.h.)
 
 // (int)x as x86-64 converts (cvttsd2si: truncation; NaN / out of range ->
 // INT_MIN), as rtw_quantize_canvas_device.

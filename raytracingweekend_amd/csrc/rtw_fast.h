@@ -426,17 +426,7 @@ constexpr int kFastBlock = 1024;
 // packet) 472; 768 at 6 (spill-free, every node in the packet, its fetch
 // shortcut) 751.  1 024 stays.
 constexpr int fast_block(int F) { return kFastBlock; }
-// LDS stack entries per lane.  The media kernel's walks are group walks
-// from an empty stack (a scene with media has no world BVH), which hold at
-// most D entries for a tree of depth D (launch_fast: group_depth), so 12
-// entries serve Book 2's trees (depths 10 and 12) where the general bound
-// (world + group depth + 2) asks for 16.  The 8 KB this frees per
-// workgroup grows the node packet from 1 534 to all 1 668 of Book 2's nodes
-// at two 1 024-thread workgroups per CU, and every node is then an LDS
-// read (node_at<PALL>): C5 fp32 32-spp slice 856 vs 828 Msamples/s
-// (+3.4 %, profiles/r06/ab_r6o_C5f.log; bit-identical, parity_r6o_mstack.log).
-constexpr int kMediaStack = 12;
-constexpr int fast_stack(int F) { return (F & rtwd::F_MEDIA) ? kMediaStack : rtwd::kLdsStack; }
+// (LDS stack entries per lane, fast_stack: rtw_select.h)
 // the all-in-packet node fetch (node_at<PALL>, a wave-uniform test)
 constexpr bool fast_pall(int F) { return true; }
 

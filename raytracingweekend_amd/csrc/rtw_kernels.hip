@@ -25,6 +25,7 @@
 // pool order never changes a result, only its speed.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -32,6 +33,7 @@
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 #include "rtw_device.h"
 #include "rtw_fast.h"
@@ -1276,14 +1278,6 @@ __device__ __forceinline__ const fast_args& fast_args_now() {
     return *(const fast_args*)p;
 }
 
-// fp32 kernels for scenes without a noise texture (F bit, fast kernels only):
-// the marble texture compiled out of shading (rtw_fast.h texture_value)
-constexpr int FF_NONOISE = 1 << 12;
-// ... and for scenes with image textures: the texel lookup and the surface
-// coordinates compiled in (rtw_fast.h image_value); without this bit no fp32
-// kernel carries them
-constexpr int FF_IMAGE = 1 << 13;
-
 // Waves per SIMD of k_fast.  With the node packet, 8 waves in two
 // 1 024-thread workgroups per CU (each with a ~48 KB packet) beat 6 waves in
 // two 768-thread ones (~56 KB packets, no spills) although the kernel then
@@ -2477,7 +2471,7 @@ int upload_scene(handle_t* h, const rtw_scene_desc* d) {
     // entry at stack position j has depth >= j + 1: true for the root at 0,
     // and an inner node of depth k popped from position k' <= k - 1 puts
     // depth-(k + 1) children at k' and k' + 1).  The fp32 media kernel's
-    // group walks are such walks (launch_fast).
+    // group walks are such walks (select_fp32).
     h->group_depth = group_depth;
     bool movers = false;
     for (int k = 0; k < d->n_prims; ++k) movers |= d->prims[k].type == RTW_PRIM_MOVING_SPHERE;
@@ -2612,84 +2606,13 @@ int upload_scene(handle_t* h, const rtw_scene_desc* d) {
     return RTW_OK;
 }
 
-// Shade kernels are instantiated for a few material/texture sets; a scene
-// runs the smallest instantiated superset of its own set.
-constexpr int SF_NOCHECKER = SF_ALL & ~SF_CHECKER;  // the Book-2 set: noise, metal, glass, media
-// Scenes with image textures (SF_IMAGE) run one set: everything.  A scene
-// without them matches one of the sets before it, as it always did.
-constexpr int SF_IMG_ALL = SF_ALL | SF_IMAGE;
-constexpr int kShadeMasks[] = {SF_DIEL, SF_METAL | SF_DIEL, SF_NOISE, SF_NOCHECKER, SF_ALL, SF_IMG_ALL};
-
-constexpr uint32_t kShadeLdsMax = 40 * 1024;
-
-int pick_shade_mask(int mask) {
-    for (int cand : kShadeMasks)
-        if ((mask & ~cand) == 0) return cand;
-    return SF_IMG_ALL;
-}
-
-// Kernel names as rocprofv3 demangles them ("k_persist_sort<112, 8, true>"),
-// for rtw_scene_query and the bench's PMC bookkeeping.
-std::string kname(const char* k, int f, int m, int lds = -1, int lst = -1) {
-    std::string s = std::string(k) + "<" + std::to_string(f);
-    if (m >= 0) s += ", " + std::to_string(m);
-    if (lds >= 0) s += lds ? ", true" : ", false";
-    if (lst >= 0) s += lst ? ", true" : ", false";
-    return s + ">";
-}
-
-// Fused traversal + shading for the common scene shapes; returns false when
-// no fused instantiation covers (features, material set), and the caller
-// then runs the split k_intersect / k_shade pair.  probe: only report (and
-// name the kernel in *name when given).
-bool launch_segment(bool probe, int f, int mask, int grid, hipStream_t st, const scene& S, const job_t& J,
-                    const paths_t& A, const fresh_t& FR, ctrs_t* C, const char* base, uint32_t bytes,
-                    std::string* name = nullptr) {
-    const int pick = pick_shade_mask(mask);
-    const bool lds = bytes <= kShadeLdsMax;
-    const size_t shm = lds ? bytes : 0;
-#ifndef RTW_SUBSET
-    // image scenes: the list and the world-BVH forms, scene data through the
-    // caches; any other feature set takes the split pair (k_shade<SF_IMG_ALL>)
-#define RTW_SEG_IMG(FF)                                                                                        \
-    if ((pick & SF_IMAGE) && f == (FF)) {                                                                    \
-        if (name) *name = kname("k_segment", FF, SF_IMG_ALL, 0);                                             \
-        if (!probe)                                                                                           \
-            hipLaunchKernelGGL((k_segment<FF, SF_IMG_ALL, false>), dim3(grid), dim3(kBlock), 0, st, S, J, A, FR, C, \
-                               base, bytes);                                                                 \
-        return true;                                                                                         \
-    }
-    RTW_SEG_IMG(0)
-    RTW_SEG_IMG(F_WBVH)
-#undef RTW_SEG_IMG
-#endif
-    if (pick & SF_IMAGE) return false;
-#define RTW_SEG(FF, MM, LL)                                                                                    \
-    if (f == (FF) && pick == (MM) && lds == (LL)) {                                                          \
-        if (name) *name = kname("k_segment", FF, MM, LL);                                                    \
-        if (!probe)                                                                                           \
-            hipLaunchKernelGGL((k_segment<FF, MM, LL>), dim3(grid), dim3(kBlock), shm, st, S, J, A, FR, C, base, bytes); \
-        return true;                                                                                         \
-    }
-#ifndef RTW_SUBSET
-    RTW_SEG(0, SF_DIEL, true)
-    RTW_SEG(0, SF_METAL | SF_DIEL, true)
-    RTW_SEG(0, SF_ALL, true)
-    RTW_SEG(0, SF_ALL, false)
-    RTW_SEG(F_WBVH, SF_ALL, false)
-    RTW_SEG(F_WBVH, SF_ALL, true)
-#endif
-#undef RTW_SEG
-    return false;
-}
-
 // Resident workgroups per CU of kernel `fn` at `block` threads and `shm`
 // bytes of dynamic LDS on the current device: one occupancy query per
 // (kernel, block, LDS bytes, device), cached.  rtw_render_multi renders from
 // one host thread per device at once, so the cache is guarded.  Returns 0
 // when the block does not fit at all and -1 when the query itself fails (not
-// cached): the packet probes and the LDS guard read -1 as "does not fit", only
-// grid sizing (grid_blocks) falls back to 2 workgroups per CU.
+// cached): the packet search reads -1 as "does not fit", only grid sizing
+// (grid_blocks) falls back to 2 workgroups per CU.
 int blocks_per_cu(const void* fn, int block, size_t shm) {
     static std::mutex mu;
     static std::map<std::tuple<const void*, int, size_t, int>, int> cache;
@@ -2709,60 +2632,34 @@ int blocks_per_cu(const void* fn, int block, size_t shm) {
     return nb;
 }
 
-// Grid of a persistent launch: resident workgroups per CU x CUs; a failed
+// Grid of a persistent launch: the number of blocks that can be resident at
+// once (workgroups per CU x CUs), so every block starts immediately; a failed
 // occupancy query assumes 2 per CU, a block that does not fit still gets 1
-// per CU (the LDS guards in the launchers refuse those before this).
+// per CU.
 int grid_blocks(const void* fn, int block, size_t shm, int cus) {
     const int nb = blocks_per_cu(fn, block, shm);
     return (nb < 0 ? 2 : std::max(1, nb)) * cus;
 }
 
-// Persistent kernel for the same instantiation set.  The grid is the number
-// of blocks that can be resident at once, so every block starts immediately.
-template <int FF, int MM, bool LL, bool LST>
-int persist_grid(size_t shm, int cus) {
-    return grid_blocks(reinterpret_cast<const void*>(&k_persist<FF, MM, LL, LST>), kPBlock, shm, cus);
-}
-
-template <int FF, int MM, bool LL>
-int persist_sort_grid(size_t shm, int cus) {
-    return grid_blocks(reinterpret_cast<const void*>(&k_persist_sort<FF, MM, LL>), kSortBlock, shm, cus);
-}
-
-// The persistent kernels: material-regrouping k_persist_sort for list
-// traversal, plain k_persist under a BVH (measured, 1 MI355X: Cornell +14 %,
-// random_balls flat +12 %, Book-2 flat +37 % with regrouping; random_balls
-// BVH -8 %, Book-2 BVH -2 %: divergent BVH walks dominate there and the
-// per-iteration block barriers cost).  RTW_SORT=0/1 forces either (A/B, tests).
-bool sort_forced(bool& value) {
-    const char* e = std::getenv("RTW_SORT");
-    if (!(e && *e)) return false;
-    value = std::atoi(e) != 0;
-    return true;
-}
-
-// BVH node packet of a k_persist<.., LST> launch: the most top nodes (BFS
-// numbering, rtw_scene_upload) that fit in LDS beside the kernel's own
-// arrays and the shading prefix without costing a workgroup per CU
-// (occupancy query per candidate size).  RTW_LDS_NODES=<n> caps it (0 = off:
-// A/B).  The node count of the last launch or probe is kept for
-// rtw_scene_query.
-thread_local uint32_t g_node_packet = 0;
+// BVH node packet of a launch with LDS stacks (k_persist<.., true>,
+// k_fast<.., true>): the most top nodes (BFS numbering, rtw_scene_upload)
+// that fit in LDS beside the kernel's own arrays and the `shm` bytes of
+// shading data without costing a workgroup per CU (occupancy query per
+// candidate size; a size that does not fit ends the search, so a launch with
+// the packet always fits).  RTW_LDS_NODES=<n> caps it (0 = off: A/B).
 constexpr size_t kPacketNodeBytes = sizeof(node_store);
-template <int FF, int MM, bool LL>
-uint32_t node_packet(size_t shm, int n_nodes) {
+uint32_t node_packet(const void* fn, int block, size_t shm, int n_nodes) {
     const char* e = std::getenv("RTW_LDS_NODES");
     uint32_t cap = (e && *e) ? (uint32_t)std::max(0, std::atoi(e)) : 4096u;
     cap = std::min<uint32_t>(cap, (uint32_t)std::max(0, n_nodes));
     if (!cap) return 0;
-    const void* fn = reinterpret_cast<const void*>(&k_persist<FF, MM, LL, true>);
-    const int base = blocks_per_cu(fn, kPBlock, shm);
+    const int base = blocks_per_cu(fn, block, shm);
     if (base <= 0) return 0;
     const size_t off = (shm + 15) & ~size_t(15);
     uint32_t best = 0;
     for (uint32_t k = 32; k <= cap + 31; k += 32) {
         const uint32_t kk = std::min(k, cap);
-        if (blocks_per_cu(fn, kPBlock, off + kk * kPacketNodeBytes) < base) break;
+        if (blocks_per_cu(fn, block, off + kk * kPacketNodeBytes) < base) break;
         best = kk;
         if (kk == cap) break;
     }
@@ -2780,277 +2677,161 @@ inline int strict_grid(int grid, const job_t& J) {
     return grid;
 #endif
 }
-template <int FF, int MM, bool LL>
-void launch_pk(bool probe, std::string* name, int cus, size_t shm, hipStream_t st, const scene& S, const job_t& J,
-               ctrs_t* C, const char* base, uint32_t bytes, int stack_need) {
-    g_node_packet = 0;
-    static const bool sorted = [] {
-        bool v;
-        // (the strict build folds each path's factors in k_persist)
-        return !RTW_STRICT_RADIANCE && (sort_forced(v) ? v : (FF & (F_WBVH | F_GBVH)) == 0);
-    }();
-    if (sorted) {
-        if (name) *name = kname("k_persist_sort", FF, MM, LL);
-        if (!probe)
-            hipLaunchKernelGGL((k_persist_sort<FF, MM, LL>), dim3(persist_sort_grid<FF, MM, LL>(shm, cus)),
-                               dim3(kSortBlock), shm, st, persist_args{S, J, C, base, bytes});
-    } else if ((FF & (F_WBVH | F_GBVH)) && stack_need <= kLdsStack &&
-               S.n_nodes < 65536) {  // 16-bit LDS stacks
-        if (name) *name = kname("k_persist", FF, MM, LL, true);
-        uint32_t packet = node_packet<FF, MM, LL>(shm, S.n_nodes);
-        const uint32_t off = (uint32_t)((shm + 15) & ~size_t(15));
-        // a launch whose LDS does not fit would fault: no packet then
-        if (packet && blocks_per_cu(reinterpret_cast<const void*>(&k_persist<FF, MM, LL, true>), kPBlock,
-                                    off + packet * kPacketNodeBytes) <= 0)
-            packet = 0;
-        g_node_packet = packet;
-        const size_t shm2 = packet ? off + packet * kPacketNodeBytes : shm;
-        if (!probe)
-            hipLaunchKernelGGL((k_persist<FF, MM, LL, true>), dim3(strict_grid(persist_grid<FF, MM, LL, true>(shm, cus), J)),
-                               dim3(kPBlock), shm2, st, persist_args{S, J, C, base, bytes, packet, off});
-    } else {
-        if (name) *name = kname("k_persist", FF, MM, LL, false);
-        if (!probe)
-            hipLaunchKernelGGL((k_persist<FF, MM, LL, false>), dim3(strict_grid(persist_grid<FF, MM, LL, false>(shm, cus), J)),
-                               dim3(kPBlock), shm, st, persist_args{S, J, C, base, bytes});
-    }
+
+// The launch tables: one row per entry of rtw_select.h's instantiation lists,
+// in their order.  These rows are what instantiates the kernels.
+struct persist_row {
+    const void *sort, *plain, *lst;  // k_persist_sort<f, m, l>, k_persist<f, m, l, false / true>
+};
+template <size_t... I>
+std::array<persist_row, sizeof...(I)> persist_rows(std::index_sequence<I...>) {
+    return {persist_row{
+        reinterpret_cast<const void*>(&k_persist_sort<kPersistList[I].f, kPersistList[I].m, kPersistList[I].l>),
+        reinterpret_cast<const void*>(&k_persist<kPersistList[I].f, kPersistList[I].m, kPersistList[I].l, false>),
+        reinterpret_cast<const void*>(&k_persist<kPersistList[I].f, kPersistList[I].m, kPersistList[I].l, true>)}...};
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> segment_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_segment<kSegmentList[I].f, kSegmentList[I].m, kSegmentList[I].l>)...};
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> fast_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_fast<kFastList[I].f, kFastList[I].l>)...};
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> fast_sort_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_fast_sort<kFastSortList[I].f, kFastSortList[I].l>)...};
+}
+const auto kPersistRows = persist_rows(std::make_index_sequence<kPersistList.size()>{});
+const auto kSegmentRows = segment_rows(std::make_index_sequence<kSegmentList.size()>{});
+const auto kFastRows = fast_rows(std::make_index_sequence<kFastList.size()>{});
+const auto kFastSortRows = fast_sort_rows(std::make_index_sequence<kFastSortList.size()>{});
+
+template <class... A>
+void launch(const void* fn, int grid, int block, size_t shm, hipStream_t st, A... a) {
+    void* args[] = {&a...};
+    (void)hipLaunchKernel(fn, dim3(grid), dim3(block), args, shm, st);  // (callers check hipGetLastError)
 }
 
-bool launch_persist(bool probe, int f, int mask, int cus, hipStream_t st, const scene& S, const job_t& J, ctrs_t* C,
-                    const char* base, uint32_t bytes, int stack_need = kStack, bool ysph = false,
-                    bool static_scene = false, bool lights = false, bool black = false, bool pin = false,
-                    std::string* name = nullptr) {
-    const int pick = pick_shade_mask(mask);
-    if (pick & SF_IMAGE) {
-        // Scenes with image textures: one persistent instantiation for list
-        // scenes (y-sphere runs take group_scan: same results) and one for a
-        // world BVH, every material and texture, scene data through the
-        // caches.  Any other feature set (media, group BVHs) has no persistent
-        // form and falls back to the wavefront kernels, which cover it.
-#ifndef RTW_SUBSET
-        if (f == 0) {
-            launch_pk<0, SF_IMG_ALL, false>(probe, name, cus, 0, st, S, J, C, base, bytes, stack_need);
-            return true;
-        }
-        if (f == F_WBVH) {
-            launch_pk<F_WBVH, SF_IMG_ALL, false>(probe, name, cus, 0, st, S, J, C, base, bytes, stack_need);
-            return true;
-        }
-#endif
-        return false;
-    }
-    if (ysph && !(f & (F_WBVH | F_MEDIA))) f |= F_YSPH;  // world runs are walked: y-sphere scans
-    // specialised kernels only
-    const int fs = f | (static_scene ? F_STATIC : 0) | (lights ? F_LIGHTS : F_NOLIGHTS) | (black ? F_BLACK : 0);
-    const bool lds = bytes <= kShadeLdsMax;
-    const size_t shm = lds ? bytes : 0;
-    // the BVH kernels' pinhole forms (F_PIN: camera batches without
-    // origins, a larger node packet) for renders whose camera allows it
-    if (pin) {
-#define RTW_PIN(FF, MM, LL)                                                                    \
-        if ((fs | F_PIN) == (FF) && pick == (MM) && lds == (LL)) {                             \
-            launch_pk<FF, MM, LL>(probe, name, cus, shm, st, S, J, C, base, bytes, stack_need); \
-            return true;                                                                       \
-        }
-        // Measured (1 MI355X, A/B, profiles/r04/ab_pin_quad_boxrcp.log): C5
-        // slice 656.1 vs 644.8 Msamples/s (the packet then holds all 1 668 of
-        // Book 2's nodes); C3 2 918 vs 2 933 (its 969 nodes fit already): the
-        // Book-2 kernel only.
-#ifndef RTW_SUBSET
-        RTW_PIN(F_MEDIA | F_GBVH | F_LIGHTS | F_BLACK | F_PIN, SF_NOCHECKER, false)
-#endif
-#undef RTW_PIN
-    }
-#define RTW_PER(FF, MM, LL)                                                                     \
-    if ((f == (FF) || fs == (FF)) && pick == (MM) && lds == (LL)) {                           \
-        launch_pk<FF, MM, LL>(probe, name, cus, shm, st, S, J, C, base, bytes, stack_need);   \
-        return true;                                                                          \
-    }
-    // specialised: small list scenes whose shading data fit in LDS, and the
-    // lambertian / metal / dielectric sets of the Book-1 scene, flat or BVH
-#ifndef RTW_SUBSET
-    RTW_PER(F_STATIC | F_LIGHTS | F_BLACK, SF_DIEL, true)
-    RTW_PER(F_STATIC | F_LIGHTS, SF_DIEL, true)
-    RTW_PER(0, SF_DIEL, true)
-    RTW_PER(0, SF_METAL | SF_DIEL, true)
-    RTW_PER(0, SF_ALL, true)
-    RTW_PER(0, SF_METAL | SF_DIEL, false)
-    RTW_PER(F_YSPH | F_NOLIGHTS, SF_METAL | SF_DIEL, false)
-    RTW_PER(F_YSPH, SF_METAL | SF_DIEL, false)
-    RTW_PER(F_WBVH | F_NOLIGHTS, SF_METAL | SF_DIEL, false)
-    RTW_PER(F_WBVH, SF_METAL | SF_DIEL, false)
-    // media scenes without checker textures (Book 2): the checker's sines
-    // and texture recursion compiled out halves the kernel's SGPR spills
-    RTW_PER(F_MEDIA | F_GBVH | F_LIGHTS | F_BLACK, SF_NOCHECKER, false)
-    RTW_PER(F_MEDIA | F_GBVH, SF_NOCHECKER, false)
-    RTW_PER(F_MEDIA, SF_NOCHECKER, false)
-#else
-    // experiment builds (scripts/ru_kernel.sh): one persistent kernel only
-    RTW_PER(RTW_SUBSET_F, RTW_SUBSET_M, RTW_SUBSET_L)
-#endif
-#undef RTW_PER
-    // general: every material / texture, scene read through the caches, one
-    // instantiation per traversal feature set (a world BVH never holds media)
-#define RTW_PER(FF)                                                                          \
-    if (f == (FF)) {                                                                       \
-        launch_pk<FF, SF_ALL, false>(probe, name, cus, 0, st, S, J, C, base, bytes, stack_need); \
-        return true;                                                                       \
-    }
-#ifndef RTW_SUBSET
-    RTW_PER(0)
-    RTW_PER(F_YSPH)
-    RTW_PER(F_MEDIA)
-    RTW_PER(F_WBVH)
-    RTW_PER(F_GBVH)
-    RTW_PER(F_YSPH | F_GBVH)
-    RTW_PER(F_MEDIA | F_GBVH)
-    RTW_PER(F_WBVH | F_GBVH)
-#endif
-#undef RTW_PER
-    return false;
+// The environment of the choice.  RTW_MODE and RTW_SPLIT are read at every
+// call, RTW_SORT and RTW_FAST_SORT once per process.
+select_env read_env() {
+    const auto flag = [](const char* name) {  // -1 unset or empty, else 0 / 1
+        const char* e = std::getenv(name);
+        return (e && *e) ? (std::atoi(e) != 0 ? 1 : 0) : -1;
+    };
+    static const int sort = flag("RTW_SORT"), fast_sort = flag("RTW_FAST_SORT");
+    const char* mode = std::getenv("RTW_MODE");
+    return {mode && std::string(mode) == "wavefront", flag("RTW_SPLIT") == 1, sort, fast_sort != 0};
 }
 
-// BVH node packet of a k_fast<.., LST> launch: the most top nodes that fit
-// in LDS beside the stacks without costing a workgroup per CU (node_packet's
-// rule; RTW_LDS_NODES caps it, 0 = off).
-uint32_t fast_node_packet(const void* fn, int n_nodes, int block) {
-    const char* e = std::getenv("RTW_LDS_NODES");
-    uint32_t cap = (e && *e) ? (uint32_t)std::max(0, std::atoi(e)) : 4096u;
-    cap = std::min<uint32_t>(cap, (uint32_t)std::max(0, n_nodes));
-    if (!cap) return 0;
-    const int base = blocks_per_cu(fn, block, 0);
-    if (base <= 0) return 0;
-    uint32_t best = 0;
-    for (uint32_t k = 32; k <= cap + 31; k += 32) {
-        const uint32_t kk = std::min(k, cap);
-        if (blocks_per_cu(fn, block, kk * sizeof(node_store)) < base) break;
-        best = kk;
-        if (kk == cap) break;
-    }
-    return best;
+// What selection reads of an uploaded scene; pin: the camera is a pinhole.
+select_in scene_facts(const handle_t* h, bool pin) {
+    select_in s;
+    s.features = h->features, s.shade_mask = h->shade_mask;
+    s.shade_bytes = h->shade_bytes, s.f32_bytes = h->f32_bytes;
+    s.stack_need = h->stack_need, s.group_depth = h->group_depth, s.n_nodes = h->S.n_nodes;
+    s.ysph = h->ysph, s.static_scene = !h->movers, s.lights = h->S.n_lights > 0;
+    s.black = h->S.background != RTW_BG_GRADIENT && h->S.render_type != RTW_RENDER_NORMAL;
+    s.pin = pin;
+    s.strict = RTW_STRICT_RADIANCE != 0;
+    return s;
 }
 
-// The fp32 fast-mode kernel of a scene: one instantiation per traversal
-// feature set, LDS stacks when the deepest walk fits them.  grid = resident
-// blocks (occupancy query, cached).  probe: name it only.
-template <int FF, bool LST>
-void launch_fast_t(bool probe, std::string* name, int cus, hipStream_t st, const fast_args& A) {
-    if (name) *name = kname("k_fast", FF, -1, LST ? 1 : 0);
-    if (probe) return;
-    const void* fn = reinterpret_cast<const void*>(&k_fast<FF, LST>);
-    fast_args a = A;
-    constexpr int blk = rtwf::fast_block(FF);
-    a.lds_nodes = LST ? fast_node_packet(fn, A.S.n_nodes, blk) : 0u;
-    const size_t shm = (size_t)a.lds_nodes * sizeof(node_store);
-    const int grid = grid_blocks(fn, blk, shm, cus);
-    hipLaunchKernelGGL((k_fast<FF, LST>), dim3(grid), dim3(blk), shm, st, a);
-}
-template <int FF, bool LL>
-void launch_fast_sort_t(bool probe, std::string* name, int cus, hipStream_t st, const fast_args& A,
-                        const char* base, uint32_t bytes) {
-    if (name) *name = kname("k_fast_sort", FF, -1, LL ? 1 : 0);
-    if (probe) return;
-    const size_t shm = LL ? bytes : 0;
-    const int grid = grid_blocks(reinterpret_cast<const void*>(&k_fast_sort<FF, LL>), kSortBlock, shm, cus);
-    fast_args a = A;  // the arrays' offsets in the LDS copy (lds_fscene_off)
-    const void* ptrs[9] = {A.S.prims, A.S.entries, A.S.ops, A.S.materials, A.S.textures,
-                           A.S.lights, A.S.ranvec, A.S.perm, A.S.frames};
-    for (int k = 0; k < 9; ++k) {
-        const char* c = static_cast<const char*>(ptrs[k]);
-        a.lds_off[k] = (c && base && c >= base && c < base + bytes) ? (uint32_t)(c - base) : ~0u;
-    }
-    hipLaunchKernelGGL((k_fast_sort<FF, LL>), dim3(grid), dim3(kSortBlock), shm, st, a, base, bytes);
-}
-// RTW_FAST_SORT=0: list scenes take k_fast too (A/B)
-bool fast_sort_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("RTW_FAST_SORT");
-        return !(e && *e && std::atoi(e) == 0);
-    }();
-    return on;
-}
-// the stack a persistent fp64 launch with LDS stacks needs
-int lst_stack_need(const handle_t* h) { return h->stack_need; }
 // fp32 renders of a scene with image textures exist for list and world-BVH
-// scenes (launch_fast); media or group BVHs with images: fp64 only.
+// scenes (select_fp32); media or group BVHs with images: fp64 only.
 bool fast_image_ok(const handle_t* h) {
     const int f = h->features & (F_MEDIA | F_WBVH | F_GBVH);
     return !(h->shade_mask & SF_IMAGE) || f == 0 || f == F_WBVH;
 }
-void launch_fast(bool probe, const handle_t* h, hipStream_t st, const fast_args& A, std::string* name = nullptr) {
-    const int f = h->features & (F_MEDIA | F_WBVH | F_GBVH);
-#ifndef RTW_SUBSET_FAST
-    if (h->shade_mask & SF_IMAGE) {
-        // scenes with image textures: k_fast with the lookup compiled in, for
-        // list scenes and world-BVH scenes (fast_image_ok: others are refused
-        // before any launch)
-        const bool lst = f == F_WBVH && h->stack_need <= rtwf::fast_stack(f) && h->S.n_nodes < 65536;
-        if (f == 0) launch_fast_t<FF_IMAGE, false>(probe, name, h->cus, st, A);
-        else if (lst) launch_fast_t<F_WBVH | FF_IMAGE, true>(probe, name, h->cus, st, A);
-        else launch_fast_t<F_WBVH | FF_IMAGE, false>(probe, name, h->cus, st, A);
-        return;
+
+// A render's kernel under the current environment: the choice, its row of the
+// launch tables and its LDS layout.  Launches nothing (occupancy queries only).
+struct plan_t {
+    kernel_choice c;
+    const void* fn = nullptr;  // the kernel (the split pair: none, launch_intersect / launch_shade)
+    size_t shm = 0;            // LDS bytes of the scene's shading data (0: read through the caches)
+    uint32_t packet = 0;       // BVH nodes staged in LDS (persist_lst, fast with LDS stacks)
+};
+int plan_render(const handle_t* h, bool pin, bool fast, plan_t* out) {
+    select_in s = scene_facts(h, pin);
+    s.env = read_env();
+    plan_t p{fast ? select_fp32(s) : select_fp64(s)};
+    const inst& id = p.c.id;
+    p.shm = !id.l ? 0 : p.c.form == kform::fast_sort ? h->f32_bytes : p.c.form == kform::fast ? 0 : h->shade_bytes;
+    const kform form = p.c.form;
+    const bool fp64 = form == kform::persist_sort || form == kform::persist || form == kform::persist_lst;
+    const int at = fp64 ? index_of(kPersistList, id) : form == kform::segment ? index_of(kSegmentList, id)
+                 : form == kform::fast ? index_of(kFastList, id)
+                 : form == kform::fast_sort ? index_of(kFastSortList, id) : 0;
+    if (at < 0) return rtw_fail(RTW_ERR_HIP, "no such instantiation: " + p.c.name);
+    if (fp64) {
+        const persist_row& r = kPersistRows[at];
+        p.fn = form == kform::persist_sort ? r.sort : form == kform::persist ? r.plain : r.lst;
+        if (form == kform::persist_lst) p.packet = node_packet(p.fn, kPBlock, p.shm, h->S.n_nodes);
+    } else if (form == kform::segment) {
+        p.fn = kSegmentRows[at];
+    } else if (form == kform::fast) {
+        p.fn = kFastRows[at];
+        if (id.l) p.packet = node_packet(p.fn, rtwf::fast_block(id.f), 0, h->F32.n_nodes);
+    } else if (form == kform::fast_sort) {
+        p.fn = kFastSortRows[at];
     }
-#endif
-#ifdef RTW_SUBSET_FAST  // experiment builds (scripts/ru_kernel.sh): the list scenes' fp32 kernel only
-#ifdef RTW_SUBSET_FAST_F  // ... or one BVH kernel k_fast<RTW_SUBSET_FAST_F, true>
-    launch_fast_t<RTW_SUBSET_FAST_F, true>(probe, name, h->cus, st, A);
-#else
-    launch_fast_sort_t<FF_NONOISE, true>(probe, name, h->cus, st, A, static_cast<const char*>(h->scene32.p),
-                                         h->f32_bytes);
-    launch_fast_t<F_WBVH | FF_NONOISE, true>(probe, name, h->cus, st, A);
-#endif
-#else
-    if ((f & (F_WBVH | F_GBVH)) == 0 && fast_sort_enabled()) {  // list scenes: regrouping kernel
-        const char* base = static_cast<const char*>(h->scene32.p);
-        const bool lds = h->f32_bytes <= kShadeLdsMax;
-        if (f == 0 && !(h->shade_mask & SF_NOISE))  // Cornell, random_balls: no marble texture
-            lds ? launch_fast_sort_t<FF_NONOISE, true>(probe, name, h->cus, st, A, base, h->f32_bytes)
-                : launch_fast_sort_t<FF_NONOISE, false>(probe, name, h->cus, st, A, base, h->f32_bytes);
-        else if (f == F_MEDIA)
-            lds ? launch_fast_sort_t<F_MEDIA, true>(probe, name, h->cus, st, A, base, h->f32_bytes)
-                : launch_fast_sort_t<F_MEDIA, false>(probe, name, h->cus, st, A, base, h->f32_bytes);
-        else
-            lds ? launch_fast_sort_t<0, true>(probe, name, h->cus, st, A, base, h->f32_bytes)
-                : launch_fast_sort_t<0, false>(probe, name, h->cus, st, A, base, h->f32_bytes);
-        return;
-    }
-    // (media scenes have no world BVH: their walks are group walks from an
-    // empty stack, group_depth entries deep)
-    const int need = (f & F_MEDIA) ? h->group_depth : h->stack_need;
-    const bool lst = (f & (F_WBVH | F_GBVH)) && need <= rtwf::fast_stack(f) && h->S.n_nodes < 65536;
-    if (f == F_WBVH && lst && !(h->shade_mask & SF_NOISE)) {  // random_balls + BVH: no marble texture
-        launch_fast_t<F_WBVH | FF_NONOISE, true>(probe, name, h->cus, st, A);
-        return;
-    }
-    switch (f * 2 + (lst ? 1 : 0)) {
-#define RTW_FAST(FF, LL) \
-    case (FF) * 2 + (LL ? 1 : 0): launch_fast_t<FF, LL>(probe, name, h->cus, st, A); break;
-        RTW_FAST(0, false)
-        RTW_FAST(F_MEDIA, false)
-        RTW_FAST(F_GBVH, false)
-        RTW_FAST(F_GBVH, true)
-        RTW_FAST(F_WBVH, false)
-        RTW_FAST(F_WBVH, true)
-        RTW_FAST(F_WBVH | F_GBVH, false)
-        RTW_FAST(F_WBVH | F_GBVH, true)
-        RTW_FAST(F_MEDIA | F_GBVH, false)
-        RTW_FAST(F_MEDIA | F_GBVH, true)
-#undef RTW_FAST
-    default:
-        launch_fast_t<F_MEDIA | F_GBVH, false>(probe, name, h->cus, st, A);
-    }
-#endif
+    *out = p;
+    return RTW_OK;
 }
 
-void launch_shade(int mask, int grid, hipStream_t st, const scene& S, const job_t& J, const paths_t& A,
+// One pass of a persistent plan (FA: the fp32 kernels' arguments).
+void launch_persistent(const plan_t& p, const handle_t* h, hipStream_t st, const job_t& J, ctrs_t* C,
+                       const fast_args& FA) {
+    const persist_args PA{h->S, J, C, h->scene_base, h->shade_bytes};
+    switch (p.c.form) {
+    case kform::persist_sort:
+        launch(p.fn, grid_blocks(p.fn, kSortBlock, p.shm, h->cus), kSortBlock, p.shm, st, PA);
+        break;
+    case kform::persist:
+        launch(p.fn, strict_grid(grid_blocks(p.fn, kPBlock, p.shm, h->cus), J), kPBlock, p.shm, st, PA);
+        break;
+    case kform::persist_lst: {  // 16-bit LDS stacks, the node packet after the shading data
+        persist_args a = PA;
+        a.lds_nodes = p.packet;
+        a.lds_nodes_off = (uint32_t)((p.shm + 15) & ~size_t(15));
+        const size_t shm = p.packet ? a.lds_nodes_off + p.packet * kPacketNodeBytes : p.shm;
+        launch(p.fn, strict_grid(grid_blocks(p.fn, kPBlock, p.shm, h->cus), J), kPBlock, shm, st, a);
+        break;
+    }
+    case kform::fast: {
+        fast_args a = FA;
+        a.lds_nodes = p.packet;
+        const size_t shm = (size_t)p.packet * sizeof(node_store);
+        const int blk = rtwf::fast_block(p.c.id.f);
+        launch(p.fn, grid_blocks(p.fn, blk, shm, h->cus), blk, shm, st, a);
+        break;
+    }
+    case kform::fast_sort: {
+        const char* base = static_cast<const char*>(h->scene32.p);
+        const uint32_t bytes = h->f32_bytes;
+        fast_args a = FA;  // the arrays' offsets in the LDS copy (lds_fscene_off)
+        const void* ptrs[9] = {FA.S.prims, FA.S.entries, FA.S.ops, FA.S.materials, FA.S.textures,
+                               FA.S.lights, FA.S.ranvec, FA.S.perm, FA.S.frames};
+        for (int k = 0; k < 9; ++k) {
+            const char* c = static_cast<const char*>(ptrs[k]);
+            a.lds_off[k] = (c && base && c >= base && c < base + bytes) ? (uint32_t)(c - base) : ~0u;
+        }
+        launch(p.fn, grid_blocks(p.fn, kSortBlock, p.shm, h->cus), kSortBlock, p.shm, st, a, base, bytes);
+        break;
+    }
+    case kform::segment:
+    case kform::split: break;  // (wavefront_pass)
+    }
+}
+
+void launch_shade(const plan_t& p, int grid, hipStream_t st, const scene& S, const job_t& J, const paths_t& A,
                   const fresh_t& F, const double* ht, const int32_t* hid, ctrs_t* C, const char* base, uint32_t bytes) {
-    const int pick = pick_shade_mask(mask);
-    const bool lds = bytes <= kShadeLdsMax;
-    const size_t shm = lds ? bytes : 0;
-    switch (pick * 2 + (lds ? 1 : 0)) {
+    switch (p.c.id.m * 2 + (p.c.id.l ? 1 : 0)) {
 #define RTW_CASE(M, LDS)                                                                                   \
     case M * 2 + (LDS ? 1 : 0):                                                                            \
-        hipLaunchKernelGGL((k_shade<M, LDS>), dim3(grid), dim3(kBlock), shm, st, S, J, A, F, ht, hid, C, base, bytes); \
+        hipLaunchKernelGGL((k_shade<M, LDS>), dim3(grid), dim3(kBlock), p.shm, st, S, J, A, F, ht, hid, C, base, bytes); \
         break;
 #ifndef RTW_SUBSET
         RTW_CASE(SF_DIEL, true)
@@ -3060,11 +2841,7 @@ void launch_shade(int mask, int grid, hipStream_t st, const scene& S, const job_
         RTW_CASE(SF_NOISE, true)
         RTW_CASE(SF_NOISE, false)
         RTW_CASE(SF_ALL, true)
-        RTW_CASE(SF_IMG_ALL, false)
-        case SF_IMG_ALL * 2 + 1:  // (no LDS form for image scenes)
-            hipLaunchKernelGGL((k_shade<SF_IMG_ALL, false>), dim3(grid), dim3(kBlock), 0, st, S, J, A, F, ht, hid, C, base,
-                               bytes);
-            break;
+        RTW_CASE(SF_IMG_ALL, false)  // (no LDS form for image scenes: select_fp64)
 #endif
 #undef RTW_CASE
     default:
@@ -3074,10 +2851,9 @@ void launch_shade(int mask, int grid, hipStream_t st, const scene& S, const job_
 
 // one traversal kernel per scene-feature combination (a world BVH never
 // coexists with media: validate_desc)
-void launch_intersect(int f, int grid, hipStream_t st, const scene& S, const paths_t& A, const fresh_t& FR,
-                      double* ht, int32_t* hid,
-                      ctrs_t* C) {
-    switch (f) {
+void launch_intersect(const plan_t& p, int grid, hipStream_t st, const scene& S, const paths_t& A, const fresh_t& FR,
+                      double* ht, int32_t* hid, ctrs_t* C) {
+    switch (p.c.id.f) {
 #define RTW_CASE(F)                                                                               \
     case F:                                                                                       \
         hipLaunchKernelGGL(k_intersect<F>, dim3(grid), dim3(kBlock), 0, st, S, A, FR, ht, hid, C); \
@@ -3096,7 +2872,6 @@ void launch_intersect(int f, int grid, hipStream_t st, const scene& S, const pat
     }
 }
 
-
 hipEvent_t event_at(handle_t* h, size_t k) {
     while (h->events.size() <= k) {
         hipEvent_t e;
@@ -3112,28 +2887,6 @@ size_t pass_budget_samples() {
         if (v > 0) return (size_t)v;
     }
     return size_t(1) << 30;  // 24 GiB of per-sample radiance records per pass (T: one pass)
-}
-
-// The traversal kernel a render of `h` launches under the current
-// environment (RTW_MODE / RTW_SPLIT / RTW_SORT), named as rocprofv3 does.
-std::string render_kernel_name(const handle_t* h) {
-    std::string name;
-    const job_t J{};
-    const char* mode_env = std::getenv("RTW_MODE");
-    const bool wavefront = mode_env && std::string(mode_env) == "wavefront";
-    if (!wavefront && launch_persist(true, h->features, h->shade_mask, 0, nullptr, h->S, J, nullptr, h->scene_base,
-                                     h->shade_bytes, lst_stack_need(h), h->ysph, !h->movers, h->S.n_lights > 0,
-                                     h->S.background != RTW_BG_GRADIENT && h->S.render_type != RTW_RENDER_NORMAL,
-                                     h->desc_pin, &name))
-        return name;
-    const char* split_env = std::getenv("RTW_SPLIT");
-    const paths_t A{};
-    const fresh_t FR{};
-    if (!(split_env && std::atoi(split_env) != 0) &&
-        launch_segment(true, h->features, h->shade_mask, 0, nullptr, h->S, J, A, FR, nullptr, h->scene_base,
-                       h->shade_bytes, &name))
-        return name;
-    return kname("k_intersect", h->features, -1);
 }
 
 // PPM channel bytes (RayTracingWeekend.cpp:266-270): int(255.99f * c) as
@@ -3172,15 +2925,15 @@ extern "C" int rtw_scene_query(void* handle, rtw_scene_info* out) {
     out->features = h->features;
     out->shade_mask = h->shade_mask;
     out->shade_lds_bytes = h->shade_bytes <= kShadeLdsMax ? (int32_t)h->shade_bytes : 0;
-    HIPCHK(hipSetDevice(h->device));  // occupancy queries of the probe
-    g_node_packet = 0;
-    const std::string k = render_kernel_name(h);
-    out->bvh_lds_nodes = (int32_t)g_node_packet;  // set by the probe (launch_pk)
-    std::snprintf(out->kernel, sizeof out->kernel, "%s", k.c_str());
+    HIPCHK(hipSetDevice(h->device));  // occupancy queries of the plans
+    // the kernels of a render with the scene's own camera
+    plan_t p64, p32;
+    if (int rc = plan_render(h, h->desc_pin, false, &p64)) return rc;
+    if (int rc = plan_render(h, h->desc_pin, true, &p32)) return rc;
+    out->bvh_lds_nodes = (int32_t)p64.packet;
+    std::snprintf(out->kernel, sizeof out->kernel, "%s", p64.c.name.c_str());
     std::snprintf(out->build_id, sizeof out->build_id, "%s", RTW_BUILD_ID);
-    std::string kf;
-    launch_fast(true, h, nullptr, fast_args{}, &kf);
-    std::snprintf(out->kernel_fast, sizeof out->kernel_fast, "%s", kf.c_str());
+    std::snprintf(out->kernel_fast, sizeof out->kernel_fast, "%s", p32.c.name.c_str());
     return RTW_OK;
 }
 
@@ -3311,6 +3064,84 @@ extern "C" int rtw_finalize_canvas_device(void* handle, const double* accum, int
     return RTW_OK;
 }
 
+using ev_list = std::vector<std::pair<size_t, size_t>>;  // event slots around timed launches
+
+// The wavefront form's path pool and hit records.
+struct wave_pool {
+    paths_t A, B;  // ping-pong for compaction
+    fresh_t FR;
+    double* ht;
+    int32_t* hid;
+    uint32_t size;
+};
+
+// One pass of the wavefront form: fill the pool, then per iteration the plan's
+// fused k_segment or the k_intersect / k_shade pair and a refill (k_regen)
+// or, once the sample queue is drained, a compaction; ends when a status
+// snapshot shows the pool empty.  timed: render_accumulate's event helper.
+template <class T>
+int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, wave_pool& W, int max_depth, size_t& ev, T& timed,
+                   ev_list* time_isect, ev_list* time_shade, rtw_stats& stats) {
+    hipStream_t st = h->stream;
+    ctrs_t* C = static_cast<ctrs_t*>(h->ctrs.p);
+    const int grid = h->grid;
+    const int regen_grid = (int)((W.size + kRegenSlots - 1) / kRegenSlots);
+    const int check_every = 4;
+    const uint32_t n0 = std::min<uint32_t>(W.size, J.total);
+    int rc;
+    hipLaunchKernelGGL(k_fill, dim3((n0 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, W.A, C, n0);
+    hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
+    HIPCHK(hipGetLastError());
+    bool tail = false;
+    std::vector<size_t> checks;  // event slots of status copies, with their copy index
+    // every iteration retires >= 1 live segment; a pass needs at most
+    // total * max_depth / pool + max_depth iterations plus the lag of the
+    // status snapshots -- far beyond that the pool is not draining: fail
+    const uint64_t cap = (uint64_t)J.total * (uint64_t)max_depth / n0 + 4ull * max_depth + 64;
+    for (uint64_t it = 0;; ++it) {
+        if (it > cap) return rtw_fail(RTW_ERR_HIP, "wavefront did not drain (internal error)");
+        if (plan.c.form == kform::segment) {
+            rc = timed(time_isect, [&] {
+                launch(plan.fn, grid, kBlock, plan.shm, st, h->S, J, W.A, W.FR, C, h->scene_base, h->shade_bytes);
+            });
+            if (rc) return rc;
+        } else {
+            rc = timed(time_isect, [&] { launch_intersect(plan, grid, st, h->S, W.A, W.FR, W.ht, W.hid, C); });
+            if (rc) return rc;
+            rc = timed(time_shade, [&] {
+                launch_shade(plan, grid, st, h->S, J, W.A, W.FR, W.ht, W.hid, C, h->scene_base, h->shade_bytes);
+            });
+            if (rc) return rc;
+        }
+        if (!tail) hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
+        HIPCHK(hipGetLastError());
+        stats.launches_intersect++;
+        stats.iterations++;
+        if (tail) {
+            hipLaunchKernelGGL(k_compact, dim3(grid), dim3(kBlock), 0, st, W.A, W.B, C);
+            hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, st, C);
+            HIPCHK(hipGetLastError());
+            std::swap(W.A, W.B);
+        }
+        if (it % check_every == check_every - 1) {
+            // status snapshot; decide from the previous snapshot so the GPU
+            // keeps `check_every` iterations of queued work
+            const size_t slot = checks.size() % 64;
+            HIPCHK(hipMemcpyAsync(&h->host_ctrs[slot], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
+            const size_t e = ev++;
+            if (!event_at(h, e)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
+            HIPCHK(hipEventRecord(h->events[e], st));
+            checks.push_back(e);
+            const size_t idx = checks.size() >= 2 ? checks.size() - 2 : 0;
+            HIPCHK(hipEventSynchronize(h->events[checks[idx]]));
+            const ctrs_t snap = h->host_ctrs[idx % 64];
+            if (queue_drained(snap, J.total)) tail = true;
+            if (tail && snap.n == 0) break;
+        }
+    }
+    return RTW_OK;
+}
+
 // The render of rtw_render_accumulate and, with accum_sq set, of
 // rtw_render_accumulate_moments (rtw_noise.h): the same launches, allocations
 // and copies, except that k_reduce_moments takes k_reduce's place and a
@@ -3358,27 +3189,18 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
 
     // execution form: persistent (paths in registers, one launch per pass)
     // unless RTW_MODE=wavefront or no persistent instantiation covers the
-    // scene (a probe: nothing is launched); the strict build refuses the
-    // other forms here, before any allocation or launch
-    const char* mode_env = std::getenv("RTW_MODE");
+    // scene (rtw_select.h; planning launches nothing); the strict build
+    // refuses the other forms here, before any allocation or launch
     // fp32 fast mode: its own persistent kernel (rtw_fast.h), same passes,
     // radiance records and ordered per-pixel reduction
     const bool fast = R.precision == RTW_PRECISION_FP32;
     const bool pin = camera_is_pinhole(*camera);
-    bool persistent;
-    {
-        job_t J0{};
-        persistent = fast || (!(mode_env && std::string(mode_env) == "wavefront") &&
-                              launch_persist(true, h->features, h->shade_mask, 0, st, h->S, J0, nullptr,
-                                             h->scene_base, h->shade_bytes, lst_stack_need(h), h->ysph, !h->movers,
-                                             h->S.n_lights > 0,
-                                             h->S.background != RTW_BG_GRADIENT &&
-                                                 h->S.render_type != RTW_RENDER_NORMAL,
-                                             pin));
-    }
     if (fast && !fast_image_ok(h))
         return rtw_fail(RTW_ERR_UNSUPPORTED, "precision fp32 with image textures covers list and world-BVH scenes only "
                                              "(this scene has media or group BVHs): render it in fp64");
+    plan_t plan;
+    if (int rc = plan_render(h, pin, fast, &plan)) return rc;
+    const bool persistent = plan.c.persistent();
     if (RTW_STRICT_RADIANCE && !persistent)
         return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders with the persistent kernel only "
                                              "(RTW_MODE=wavefront or a scene without a persistent instantiation)");
@@ -3400,10 +3222,9 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
     if ((rc = h->radiance.ensure(pass_samples * 24))) return rc;
     if ((rc = h->run.ensure(npix * 24))) return rc;
     if (accum_sq && (rc = h->run2.ensure(npix * 24))) return rc;
-    paths_t A = carve_paths(h->pool[0].p, pool), B = carve_paths(h->pool[1].p, pool);
-    const fresh_t FR = carve_fresh(h->fresh.p, pool);
-    double* ht = static_cast<double*>(h->hits.p);
-    int32_t* hid = reinterpret_cast<int32_t*>(static_cast<char*>(h->hits.p) + (size_t)pool * 8);
+    wave_pool W{carve_paths(h->pool[0].p, pool), carve_paths(h->pool[1].p, pool), carve_fresh(h->fresh.p, pool),
+                static_cast<double*>(h->hits.p),
+                reinterpret_cast<int32_t*>(static_cast<char*>(h->hits.p) + (size_t)pool * 8), pool};
     ctrs_t* C = static_cast<ctrs_t*>(h->ctrs.p);
     double* run = static_cast<double*>(h->run.p);
     double* run2 = accum_sq ? static_cast<double*>(h->run2.p) : nullptr;
@@ -3458,25 +3279,30 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
     J.flog = static_cast<double*>(h->flog.p);
 #endif
 
-    const int grid = h->grid;
-    const int regen_grid = (int)((pool + kRegenSlots - 1) / kRegenSlots);
     size_t ev = 0;
-    std::vector<std::pair<size_t, size_t>> isect_ev, shade_ev;
+    ev_list isect_ev, shade_ev;
     hipEvent_t ev_begin = event_at(h, ev++), ev_end = event_at(h, ev++);
     if (!ev_begin || !ev_end) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
     HIPCHK(hipEventRecord(ev_begin, st));
     // collect_kernel_times: 1 = events around each traversal launch (the
     // roofline kernel), 2 = also around each shade launch.  Every event pair
     // costs a few us of queue gap per iteration, so the default is neither.
-    const bool timed = R.collect_kernel_times != 0;
-    const bool timed_shade = R.collect_kernel_times >= 2;
-    // traversal + shading fused into one kernel where an instantiation covers
-    // the scene (RTW_SPLIT=1 forces the split pair, for tests and profiling)
-    const char* split_env = std::getenv("RTW_SPLIT");
-    const bool fused = !(split_env && std::atoi(split_env) != 0) &&
-                       launch_segment(true, h->features, h->shade_mask, 0, st, h->S, J, A, FR, C, h->scene_base,
-                                      h->shade_bytes);
-    const int check_every = 4;
+    ev_list* const time_isect = R.collect_kernel_times != 0 ? &isect_ev : nullptr;
+    ev_list* const time_shade = R.collect_kernel_times >= 2 ? &shade_ev : nullptr;
+    // launch(), between two events whose slots go to *list (null: untimed)
+    auto timed = [&](ev_list* list, auto&& launch) -> int {
+        if (!list) {
+            launch();
+            return RTW_OK;
+        }
+        const size_t e0 = ev++, e1 = ev++;
+        if (!event_at(h, e1)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
+        HIPCHK(hipEventRecord(h->events[e0], st));
+        launch();
+        HIPCHK(hipEventRecord(h->events[e1], st));
+        list->push_back({e0, e1});
+        return RTW_OK;
+    };
     fast_args FA{};
     if (fast) {
         FA.S = h->F32;
@@ -3496,110 +3322,17 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
         J.spp_pass = S_pass;
         J.div_spp = rtwd::udiv_magic(S_pass);
         J.s_begin = R.spp_begin + (int)done;
-        const uint32_t n0 = std::min<uint32_t>(pool, J.total);
         if (persistent) {
-            hipLaunchKernelGGL(k_fill, dim3(1), dim3(kBlock), 0, st, A, C, 0u);  // reset the queue
-            size_t e0 = 0, e1 = 0;
-            if (timed) {
-                e0 = ev++, e1 = ev++;
-                if (!event_at(h, e1)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
-                HIPCHK(hipEventRecord(h->events[e0], st));
-            }
-            if (fast) {
-                FA.J = J;
-                launch_fast(false, h, st, FA);
-            } else {
-                launch_persist(false, h->features, h->shade_mask, h->cus, st, h->S, J, C, h->scene_base,
-                               h->shade_bytes, lst_stack_need(h), h->ysph, !h->movers, h->S.n_lights > 0,
-                               h->S.background != RTW_BG_GRADIENT && h->S.render_type != RTW_RENDER_NORMAL, pin);
-            }
+            hipLaunchKernelGGL(k_fill, dim3(1), dim3(kBlock), 0, st, W.A, C, 0u);  // reset the queue
+            FA.J = J;
+            if ((rc = timed(time_isect, [&] { launch_persistent(plan, h, st, J, C, FA); }))) return rc;
             HIPCHK(hipGetLastError());
-            if (timed) {
-                HIPCHK(hipEventRecord(h->events[e1], st));
-                isect_ev.push_back({e0, e1});
-            }
             stats.launches_intersect++;
             stats.iterations++;
-            launch_reduce(fast, J.L, S_pass);
-            HIPCHK(hipGetLastError());
-            stats.samples += J.total;
-            continue;
+        } else if ((rc = wavefront_pass(h, plan, J, W, R.max_depth, ev, timed, time_isect, time_shade, stats))) {
+            return rc;
         }
-        hipLaunchKernelGGL(k_fill, dim3((n0 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, A, C, n0);
-        hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, A, FR, C);
-        HIPCHK(hipGetLastError());
-        bool tail = false;
-        std::vector<size_t> checks;  // event slots of status copies, with their copy index
-        // every iteration retires >= 1 live segment; a pass needs at most
-        // total * max_depth / pool + max_depth iterations plus the lag of the
-        // status snapshots -- far beyond that the pool is not draining: fail
-        const uint64_t cap = (uint64_t)J.total * (uint64_t)R.max_depth / n0 + 4ull * R.max_depth + 64;
-        for (uint64_t it = 0;; ++it) {
-            if (it > cap) return rtw_fail(RTW_ERR_HIP, "wavefront did not drain (internal error)");
-            {
-                size_t e0 = 0, e1 = 0;
-                if (fused) {
-                    if (timed) {
-                        e0 = ev++, e1 = ev++;
-                        if (!event_at(h, e1)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
-                        HIPCHK(hipEventRecord(h->events[e0], st));
-                    }
-                    launch_segment(false, h->features, h->shade_mask, grid, st, h->S, J, A, FR, C, h->scene_base,
-                                   h->shade_bytes);
-                    if (timed) {
-                        HIPCHK(hipEventRecord(h->events[e1], st));
-                        isect_ev.push_back({e0, e1});
-                    }
-                } else {
-                if (timed) {
-                    e0 = ev++, e1 = ev++;
-                    if (!event_at(h, e1)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
-                    HIPCHK(hipEventRecord(h->events[e0], st));
-                }
-                launch_intersect(h->features, grid, st, h->S, A, FR, ht, hid, C);
-                if (timed) {
-                    HIPCHK(hipEventRecord(h->events[e1], st));
-                    isect_ev.push_back({e0, e1});
-                }
-                if (timed_shade) {
-                    e0 = ev++, e1 = ev++;
-                    if (!event_at(h, e1)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
-                    HIPCHK(hipEventRecord(h->events[e0], st));
-                }
-                launch_shade(h->shade_mask, grid, st, h->S, J, A, FR, ht, hid, C, h->scene_base, h->shade_bytes);
-                if (timed_shade) {
-                    HIPCHK(hipEventRecord(h->events[e1], st));
-                    shade_ev.push_back({e0, e1});
-                }
-                }
-                if (!tail) hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, A, FR, C);
-                HIPCHK(hipGetLastError());
-                stats.launches_intersect++;
-                stats.iterations++;
-                if (tail) {
-                    hipLaunchKernelGGL(k_compact, dim3(grid), dim3(kBlock), 0, st, A, B, C);
-                    hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, st, C);
-                    HIPCHK(hipGetLastError());
-                    std::swap(A, B);
-                }
-            }
-            if (it % check_every == check_every - 1) {
-                // status snapshot; decide from the previous snapshot so the GPU
-                // keeps `check_every` iterations of queued work
-                const size_t slot = checks.size() % 64;
-                HIPCHK(hipMemcpyAsync(&h->host_ctrs[slot], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
-                const size_t e = ev++;
-                if (!event_at(h, e)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
-                HIPCHK(hipEventRecord(h->events[e], st));
-                checks.push_back(e);
-                const size_t idx = checks.size() >= 2 ? checks.size() - 2 : 0;
-                HIPCHK(hipEventSynchronize(h->events[checks[idx]]));
-                const ctrs_t snap = h->host_ctrs[idx % 64];
-                if (queue_drained(snap, J.total)) tail = true;
-                if (tail && snap.n == 0) break;
-            }
-        }
-        launch_reduce(false, J.L, S_pass);  // the wavefront form is fp64 only
+        launch_reduce(fast, J.L, S_pass);  // (the wavefront form is fp64 only)
         HIPCHK(hipGetLastError());
         stats.samples += J.total;
     }

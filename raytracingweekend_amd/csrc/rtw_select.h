@@ -1,0 +1,287 @@
+// rtw_select.h — which kernel a render runs: the template arguments the
+// kernels are specialised by, the instantiations that exist, and the choice
+// among them.  Plain C++17 (no HIP): rtw_kernels.hip builds its launch tables
+// from the lists here, and tests/cpp/select_check.cpp walks the choice on the
+// CPU.
+#pragma once
+#include <array>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+namespace rtwd {
+
+// Scene features a traversal kernel is specialised for.
+// F_YSPH: the world list holds y-sphere runs (ysphere_scan); without it such
+// runs take group_scan (same results), which keeps the prefilter's code and
+// registers out of the kernels of other scenes (Cornell).
+// F_STATIC: no moving spheres, so a ray's time is never read (sphere.h:22-25
+// is its only reader); the persistent kernels then keep no time per path
+// (the camera still draws it: the RNG sequence is the reference's).
+// F_LIGHTS: the scene has lights, so every lambertian bounce samples the
+// mixture pdf (RayTracingWeekend.cpp:112-132) and the lights-free branch is
+// compiled out.
+// F_BLACK: black background and colour rendering (RayTracingWeekend.cpp:
+// 135-159): a miss emits 0 and the normal-visualisation branch is compiled out.
+// F_NOLIGHTS: the scene has no lights, so the mixture-pdf branch of the
+// lambertian bounce is compiled out instead.
+enum : int { F_MEDIA = 1, F_WBVH = 2, F_GBVH = 4, F_YSPH = 8, F_STATIC = 16, F_LIGHTS = 32, F_BLACK = 64,
+             F_NOLIGHTS = 128,
+             // every camera ray of the render starts at the camera's origin (a
+             // pinhole camera, lens_radius 0, whose origin has no zero
+             // coordinate: origin + offset is then exactly origin, camera.h:48)
+             F_PIN = 256 };
+// fp32 kernels for scenes without a noise texture (F bit, fast kernels only):
+// the marble texture compiled out of shading (rtw_fast.h texture_value)
+constexpr int FF_NONOISE = 1 << 12;
+// ... and for scenes with image textures: the texel lookup and the surface
+// coordinates compiled in (rtw_fast.h image_value); without this bit no fp32
+// kernel carries them
+constexpr int FF_IMAGE = 1 << 13;
+
+// Shade-kernel specialisation by the scene's material / texture set.
+// SF_ALL: every material and every texture but the image texture (its value
+// is part of the kernels' names); SF_IMAGE: the scene holds image textures,
+// so shading forms surface coordinates (u, v) where a texture walk reaches
+// one -- only kernels compiled with this bit carry that code.
+enum : int { SF_NOISE = 1, SF_CHECKER = 2, SF_METAL = 4, SF_DIEL = 8, SF_ISO = 16, SF_ALL = 31, SF_IMAGE = 32 };
+
+// Shade kernels are instantiated for a few material/texture sets; a scene
+// runs the smallest instantiated superset of its own set.
+constexpr int SF_NOCHECKER = SF_ALL & ~SF_CHECKER;  // the Book-2 set: noise, metal, glass, media
+// Scenes with image textures (SF_IMAGE) run one set: everything.  A scene
+// without them matches one of the sets before it, as it always did.
+constexpr int SF_IMG_ALL = SF_ALL | SF_IMAGE;
+constexpr int kShadeMasks[] = {SF_DIEL, SF_METAL | SF_DIEL, SF_NOISE, SF_NOCHECKER, SF_ALL, SF_IMG_ALL};
+
+constexpr uint32_t kShadeLdsMax = 40 * 1024;
+
+inline int pick_shade_mask(int mask) {
+    for (int cand : kShadeMasks)
+        if ((mask & ~cand) == 0) return cand;
+    return SF_IMG_ALL;
+}
+
+constexpr int kLdsStack = 16;  // LDS stack entries per lane
+
+// Kernel names as rocprofv3 demangles them ("k_persist_sort<112, 8, true>"),
+// for rtw_scene_query and the bench's PMC bookkeeping.
+inline std::string kname(const char* k, int f, int m, int lds = -1, int lst = -1) {
+    std::string s = std::string(k) + "<" + std::to_string(f);
+    if (m >= 0) s += ", " + std::to_string(m);
+    if (lds >= 0) s += lds ? ", true" : ", false";
+    if (lst >= 0) s += lst ? ", true" : ", false";
+    return s + ">";
+}
+
+}  // namespace rtwd
+
+namespace rtwf {
+
+// LDS stack entries per lane of the fp32 kernels.  The media kernel's walks
+// are group walks from an empty stack (a scene with media has no world BVH),
+// which hold at most D entries for a tree of depth D (select_fp32:
+// group_depth), so 12 entries serve Book 2's trees (depths 10 and 12) where
+// the general bound (world + group depth + 2) asks for 16.  The 8 KB this
+// frees per workgroup grows the node packet from 1 534 to all 1 668 of Book
+// 2's nodes at two 1 024-thread workgroups per CU, and every node is then an
+// LDS read (node_at<PALL>): C5 fp32 32-spp slice 856 vs 828 Msamples/s
+// (+3.4 %, profiles/r06/ab_r6o_C5f.log; bit-identical, parity_r6o_mstack.log).
+constexpr int kMediaStack = 12;
+constexpr int fast_stack(int F) { return (F & rtwd::F_MEDIA) ? kMediaStack : rtwd::kLdsStack; }
+
+}  // namespace rtwf
+
+namespace rtwd {
+
+// ---- the instantiations ----------------------------------------------------
+// One entry per compiled kernel: its template arguments <f, m, l> (the fp32
+// families have no material set: m = -1, and l is k_fast's LDS-stack flag).
+// rtw_kernels.hip instantiates exactly these (one launch-table row each).
+struct inst {
+    int f, m;
+    bool l;
+};
+constexpr bool operator==(const inst& a, const inst& b) { return a.f == b.f && a.m == b.m && a.l == b.l; }
+
+template <class L>
+constexpr int index_of(const L& list, const inst& x) {
+    for (size_t k = 0; k < list.size(); ++k)
+        if (list[k] == x) return (int)k;
+    return -1;
+}
+
+// k_persist_sort<f, m, l>, k_persist<f, m, l, false> and k_persist<f, m, l,
+// true> (LDS traversal stacks) of every entry.
+#ifndef RTW_SUBSET
+constexpr std::array kPersistList{
+    // scenes with image textures: list scenes (y-sphere runs take
+    // group_scan: same results) and a world BVH, every material and texture,
+    // scene data through the caches
+    inst{0, SF_IMG_ALL, false}, inst{F_WBVH, SF_IMG_ALL, false},
+    // the pinhole form (F_PIN: camera batches without origins, a larger node
+    // packet).  Measured (1 MI355X, A/B, profiles/r04/ab_pin_quad_boxrcp.log):
+    // C5 slice 656.1 vs 644.8 Msamples/s (the packet then holds all 1 668 of
+    // Book 2's nodes); C3 2 918 vs 2 933 (its 969 nodes fit already): the
+    // Book-2 kernel only.
+    inst{F_MEDIA | F_GBVH | F_LIGHTS | F_BLACK | F_PIN, SF_NOCHECKER, false},
+    // specialised: small list scenes whose shading data fit in LDS, and the
+    // lambertian / metal / dielectric sets of the Book-1 scene, flat or BVH
+    inst{F_STATIC | F_LIGHTS | F_BLACK, SF_DIEL, true}, inst{F_STATIC | F_LIGHTS, SF_DIEL, true},
+    inst{0, SF_DIEL, true}, inst{0, SF_METAL | SF_DIEL, true}, inst{0, SF_ALL, true},
+    inst{0, SF_METAL | SF_DIEL, false}, inst{F_YSPH | F_NOLIGHTS, SF_METAL | SF_DIEL, false},
+    inst{F_YSPH, SF_METAL | SF_DIEL, false}, inst{F_WBVH | F_NOLIGHTS, SF_METAL | SF_DIEL, false},
+    inst{F_WBVH, SF_METAL | SF_DIEL, false},
+    // media scenes without checker textures (Book 2): the checker's sines
+    // and texture recursion compiled out halves the kernel's SGPR spills
+    inst{F_MEDIA | F_GBVH | F_LIGHTS | F_BLACK, SF_NOCHECKER, false}, inst{F_MEDIA | F_GBVH, SF_NOCHECKER, false},
+    inst{F_MEDIA, SF_NOCHECKER, false},
+    // general: every material / texture, scene read through the caches, one
+    // instantiation per traversal feature set (a world BVH never holds media)
+    inst{0, SF_ALL, false}, inst{F_YSPH, SF_ALL, false}, inst{F_MEDIA, SF_ALL, false}, inst{F_WBVH, SF_ALL, false},
+    inst{F_GBVH, SF_ALL, false}, inst{F_YSPH | F_GBVH, SF_ALL, false}, inst{F_MEDIA | F_GBVH, SF_ALL, false},
+    inst{F_WBVH | F_GBVH, SF_ALL, false}};
+// k_segment<f, m, l>: traversal + shading fused for the common scene shapes
+constexpr std::array kSegmentList{inst{0, SF_IMG_ALL, false}, inst{F_WBVH, SF_IMG_ALL, false},
+                                  inst{0, SF_DIEL, true},     inst{0, SF_METAL | SF_DIEL, true},
+                                  inst{0, SF_ALL, true},      inst{0, SF_ALL, false},
+                                  inst{F_WBVH, SF_ALL, false}, inst{F_WBVH, SF_ALL, true}};
+#else
+// experiment builds (scripts/ru_kernel.sh): one persistent kernel only
+constexpr std::array kPersistList{inst{RTW_SUBSET_F, RTW_SUBSET_M, RTW_SUBSET_L}};
+constexpr std::array<inst, 0> kSegmentList{};
+#endif
+
+// k_fast<f, l> and k_fast_sort<f, l> (l: the scene's fp32 shading data in LDS)
+#ifndef RTW_SUBSET_FAST
+constexpr std::array kFastList{
+    // scenes with image textures: list scenes and world-BVH scenes
+    inst{FF_IMAGE, -1, false}, inst{F_WBVH | FF_IMAGE, -1, true}, inst{F_WBVH | FF_IMAGE, -1, false},
+    inst{F_WBVH | FF_NONOISE, -1, true},  // random_balls + BVH: no marble texture
+    inst{0, -1, false}, inst{F_MEDIA, -1, false}, inst{F_GBVH, -1, false}, inst{F_GBVH, -1, true},
+    inst{F_WBVH, -1, false}, inst{F_WBVH, -1, true}, inst{F_WBVH | F_GBVH, -1, false},
+    inst{F_WBVH | F_GBVH, -1, true}, inst{F_MEDIA | F_GBVH, -1, false}, inst{F_MEDIA | F_GBVH, -1, true}};
+constexpr std::array kFastSortList{inst{FF_NONOISE, -1, true}, inst{FF_NONOISE, -1, false}, inst{F_MEDIA, -1, true},
+                                   inst{F_MEDIA, -1, false},   inst{0, -1, true},           inst{0, -1, false}};
+constexpr inst kFastFallback{F_MEDIA | F_GBVH, -1, false};  // of a feature set without a row
+#elif defined(RTW_SUBSET_FAST_F)  // experiment builds: one BVH kernel k_fast<RTW_SUBSET_FAST_F, true>
+constexpr std::array kFastList{inst{RTW_SUBSET_FAST_F, -1, true}};
+constexpr std::array<inst, 0> kFastSortList{};
+constexpr inst kFastFallback = kFastList[0];
+#else  // ... or the list scenes' fp32 kernel and random_balls + BVH's
+constexpr std::array kFastList{inst{F_WBVH | FF_NONOISE, -1, true}};
+constexpr std::array kFastSortList{inst{FF_NONOISE, -1, true}};
+constexpr inst kFastFallback = kFastList[0];
+#endif
+
+// ---- the choice --------------------------------------------------------------
+struct select_env {
+    bool wavefront = false;  // RTW_MODE=wavefront: no persistent kernel (fp64)
+    bool split = false;      // RTW_SPLIT=1: k_intersect + k_shade, not k_segment
+    int sort = -1;           // RTW_SORT: -1 unset, else 0 / 1 forces k_persist / k_persist_sort (A/B, tests)
+    bool fast_sort = true;   // RTW_FAST_SORT=0: list scenes take k_fast too (A/B)
+};
+
+// What the choice depends on: the uploaded scene, the render's camera, the
+// environment and the build.
+struct select_in {
+    int features = 0;    // F_MEDIA | F_WBVH | F_GBVH
+    int shade_mask = 0;  // SF_* set of the scene
+    uint32_t shade_bytes = 0, f32_bytes = 0;  // shading data, fp64 and fp32 (LDS when <= kShadeLdsMax)
+    int stack_need = 0, group_depth = 0;      // deepest BVH stack / group BVH
+    int n_nodes = 0;
+    bool ysph = false, static_scene = false, lights = false, black = false, pin = false;
+    select_env env;
+    bool strict = false;  // RTW_STRICT_RADIANCE build: folds each path's factors in k_persist, never sorts
+};
+
+enum class kform { persist_sort, persist, persist_lst, segment, split, fast, fast_sort };
+
+struct kernel_choice {
+    kform form;
+    inst id;  // the template arguments; split: {features, shade set, LDS shading} of k_intersect / k_shade
+    std::string name;
+    bool persistent() const { return form != kform::segment && form != kform::split; }
+};
+
+// The persistent kernels of an instantiation: material-regrouping
+// k_persist_sort for list traversal, plain k_persist under a BVH (measured,
+// 1 MI355X: Cornell +14 %, random_balls flat +12 %, Book-2 flat +37 % with
+// regrouping; random_balls BVH -8 %, Book-2 BVH -2 %: divergent BVH walks
+// dominate there and the per-iteration block barriers cost), with 16-bit LDS
+// stacks where the deepest walk and the node ids fit them.
+inline kernel_choice persist_choice(const inst& c, const select_in& s) {
+    const bool bvh = (c.f & (F_WBVH | F_GBVH)) != 0;
+    if (!s.strict && (s.env.sort >= 0 ? s.env.sort != 0 : !bvh))
+        return {kform::persist_sort, c, kname("k_persist_sort", c.f, c.m, c.l)};
+    const bool lst = bvh && s.stack_need <= kLdsStack && s.n_nodes < 65536;
+    return {lst ? kform::persist_lst : kform::persist, c, kname("k_persist", c.f, c.m, c.l, lst)};
+}
+
+// fp64.  Persistent unless RTW_MODE=wavefront: the first listed of the
+// scene's feature set with the pinhole bit (where the camera allows it), with
+// the static / lights / black-background bits, plain, and the general kernel
+// (every material, scene data through the caches).  A scene with image
+// textures has one candidate.  Without a persistent instantiation: the fused
+// k_segment where listed (and RTW_SPLIT is not set), else the split pair,
+// which covers everything and is reported as k_intersect<features>.
+inline kernel_choice select_fp64(const select_in& s) {
+    const int pick = pick_shade_mask(s.shade_mask);
+    const bool image = (pick & SF_IMAGE) != 0;  // (no LDS form for image scenes)
+    const bool lds = !image && s.shade_bytes <= kShadeLdsMax;
+    if (!s.env.wavefront) {
+        inst cand[4];
+        int n = 0;
+        if (image) {
+            cand[n++] = {s.features, pick, false};
+        } else {
+            // world runs are walked: y-sphere scans
+            const int f = s.features | (s.ysph && !(s.features & (F_WBVH | F_MEDIA)) ? F_YSPH : 0);
+            const int fs = f | (s.static_scene ? F_STATIC : 0) | (s.lights ? F_LIGHTS : F_NOLIGHTS) |
+                           (s.black ? F_BLACK : 0);
+            if (s.pin) cand[n++] = {fs | F_PIN, pick, lds};
+            cand[n++] = {fs, pick, lds};
+            cand[n++] = {f, pick, lds};
+            cand[n++] = {f, SF_ALL, false};
+        }
+        for (int k = 0; k < n; ++k)
+            if (index_of(kPersistList, cand[k]) >= 0) return persist_choice(cand[k], s);
+    }
+    const inst seg{s.features, pick, lds};
+    if (!s.env.split && index_of(kSegmentList, seg) >= 0)
+        return {kform::segment, seg, kname("k_segment", seg.f, seg.m, seg.l)};
+    return {kform::split, seg, kname("k_intersect", s.features, -1)};
+}
+
+// fp32 fast mode: always persistent (RTW_MODE and RTW_SPLIT do not apply).
+// List scenes take the regrouping k_fast_sort, BVH scenes k_fast with LDS
+// stacks when the deepest walk fits them; a feature set without a row runs
+// kFastFallback.
+inline kernel_choice select_fp32(const select_in& s) {
+    const int f = s.features & (F_MEDIA | F_WBVH | F_GBVH);
+    const bool bvh = (f & (F_WBVH | F_GBVH)) != 0;
+    kform form = kform::fast;
+    inst c{};
+    if (s.shade_mask & SF_IMAGE) {
+        // k_fast with the lookup compiled in, for list scenes and world-BVH
+        // scenes (others are refused before any launch)
+        const bool lst = f == F_WBVH && s.stack_need <= rtwf::fast_stack(f) && s.n_nodes < 65536;
+        c = f == 0 ? inst{FF_IMAGE, -1, false} : inst{F_WBVH | FF_IMAGE, -1, lst};
+    } else if (!bvh && s.env.fast_sort) {
+        // Cornell, random_balls: no marble texture
+        const int ff = f == F_MEDIA ? F_MEDIA : (s.shade_mask & SF_NOISE) ? 0 : FF_NONOISE;
+        form = kform::fast_sort;
+        c = {ff, -1, s.f32_bytes <= kShadeLdsMax};
+    } else {
+        // (media scenes have no world BVH: their walks are group walks from an
+        // empty stack, group_depth entries deep)
+        const int need = (f & F_MEDIA) ? s.group_depth : s.stack_need;
+        const bool lst = bvh && need <= rtwf::fast_stack(f) && s.n_nodes < 65536;
+        c = (f == F_WBVH && lst && !(s.shade_mask & SF_NOISE)) ? inst{F_WBVH | FF_NONOISE, -1, true} : inst{f, -1, lst};
+    }
+    if ((form == kform::fast_sort ? index_of(kFastSortList, c) : index_of(kFastList, c)) < 0)
+        form = kform::fast, c = kFastFallback;
+    return {form, c, kname(form == kform::fast ? "k_fast" : "k_fast_sort", c.f, -1, c.l)};
+}
+
+}  // namespace rtwd

@@ -198,7 +198,7 @@ def _depth(d, root):
 @pytest.mark.parametrize("seed", range(4))
 def test_group_walk_stack_depth_bound(render_mod, seed):
     """The fp32 media kernel sizes its LDS stacks by the deepest group BVH
-    (rtw_fast.h kMediaStack, rtw_kernels.hip launch_fast): a walk from an
+    (rtw_select.h kMediaStack, select_fp32): a walk from an
     empty stack that pops one node and pushes both children of an inner one
     never holds more than D entries for a tree of depth D.  Replays that walk
     (rtw_fast.h group_bvh pushes right, then left; the fp64 walks push the
