@@ -119,7 +119,10 @@ typedef struct rtw_entry {
  * prim indices of the group, or RTW_ITEM_BOX | i for the six rects
  * [i, i+6) of one box (hittable_list.h:65-114: xy, xy, xz, xz, yz, yz in that
  * list order), tested together as one leaf object; items of the world BVH
- * are entry indices. */
+ * are entry indices.  A group BVH leaf holds at most 16 items (the fp32 walk's
+ * node copy keeps a leaf's count in [-16, -2] and reads anything below as an
+ * inline pair of items); rtw_scene_upload refuses a larger one with
+ * RTW_ERR_UNSUPPORTED.  World BVH leaves have no limit. */
 #define RTW_ITEM_BOX 0x40000000
 #define RTW_ITEM_INDEX 0x3fffffff
 typedef struct rtw_bvh_node {

@@ -8,7 +8,9 @@ Writes, for the parity tests (which must run where the reference is absent):
   scene_<name>.json      dump of the reference scene graph (every field)
   perlin.json            Perlin tables + noise/turb/texture known answers
   render_<case>.npy      per-pixel radiance sums (float64, nx*ny*3)
-  renders.json           the cases: scene, size, spp, depth, seed, segments
+  renders.json           the cases: scene, size, spp, depth, seed, segments and,
+                         for a render in the reference's RenderType::Normal,
+                         "render_type": "normal" (absent: shaded)
   ppm_<case>.ppm         whole images as the reference writes them
                          (RayTracingWeekend.cpp:235-276: average, gamma 2,
                          clamp, P3 rows ny-1..0, int(255.99f * c))
@@ -30,7 +32,7 @@ OUT = ROOT / "tests" / "golden"
 SCENES = [("cornell_box", 1.0), ("random_balls", 1.5), ("dielectric", 2.0), ("light_sample", 2.0),
           ("book2_final", 1.0), ("nested", 1.0), ("nested_plain", 1.0)]
 
-# (case, scene, nx, ny, spp, depth, seed)
+# (case, scene, nx, ny, spp, depth, seed[, render_type])
 RENDERS = [
     ("cornell_32x32x4_d50", "cornell_box", 32, 32, 4, 50, 0),
     ("cornell_24x24x3_d100", "cornell_box", 24, 24, 3, 100, 5),
@@ -43,6 +45,14 @@ RENDERS = [
     ("nested_24x24x4_d50", "nested", 24, 24, 4, 50, 0),
     ("nested_32x24x3_d20", "nested", 32, 24, 3, 20, 3),
     ("nested_plain_24x24x4_d50", "nested_plain", 24, 24, 4, 50, 1),
+    # the group-BVH test scenes (ours, composed in ref_harness.cpp)
+    ("grouped_32x24x4_d50", "grouped", 32, 24, 4, 50, 0),
+    ("grouped_world_32x24x4_d50", "grouped_world", 32, 24, 4, 50, 2),
+    # RenderType::Normal: 0.5 (n + 1) at the first hit
+    ("cornell_normal_32x32x4", "cornell_box", 32, 32, 4, 50, 0, "normal"),
+    ("random_balls_normal_48x32x4", "random_balls", 48, 32, 4, 50, 1, "normal"),
+    ("nested_normal_24x24x4", "nested", 24, 24, 4, 50, 2, "normal"),
+    ("book2_final_normal_16x16x2", "book2_final", 16, 16, 2, 50, 3, "normal"),
 ]
 
 # whole-image P3 files (case, scene, nx, ny, spp, depth, seed)
@@ -68,14 +78,18 @@ def main() -> int:
         (OUT / f"scene_{name}.json").write_text(json.dumps(dump, separators=(",", ":")))
     (OUT / "perlin.json").write_text(json.dumps(json.loads(run("perlin")), separators=(",", ":")))
     meta = []
-    for case, scene, nx, ny, spp, depth, seed in RENDERS:
+    for case, scene, nx, ny, spp, depth, seed, *rest in RENDERS:
+        render_type = rest[0] if rest else "shaded"
         path = OUT / f"render_{case}.bin"
-        info = json.loads(run("render", scene, nx, ny, spp, depth, seed, 8, path).strip().splitlines()[-1])
+        name = scene if render_type == "shaded" else f"{render_type}:{scene}"
+        info = json.loads(run("render", name, nx, ny, spp, depth, seed, 8, path).strip().splitlines()[-1])
         sums = np.fromfile(path, dtype=np.float64)
         path.unlink()
         np.save(OUT / f"render_{case}.npy", sums)
         meta.append({"case": case, "scene": scene, "nx": nx, "ny": ny, "spp": spp, "max_depth": depth,
                      "seed": seed, "segments": info["segments"]})
+        if render_type != "shaded":
+            meta[-1]["render_type"] = render_type
     (OUT / "renders.json").write_text(json.dumps(meta, indent=1))
     ppm_meta = []
     for case, scene, nx, ny, spp, depth, seed in PPMS:

@@ -29,6 +29,7 @@
 //   bench  <name> <nx> <ny> <spp> <depth> <seed> <threads> [row_stride]
 //          times render() over every row_stride-th row (default: all rows)
 //   perlin                                  Perlin tables + noise/turb samples
+// A scene name "normal:<name>" is <name> with RenderType::Normal.
 #include "rng_inject.h"
 
 #include <cfloat>
@@ -216,7 +217,86 @@ public:
     }
 };
 
+// ---------------------------------------------------------------------------
+// Group-BVH test scene (ours; scenes.cpp builds the same with the library's
+// host API): gradient sky, no medium, no light list; a ground sphere, a
+// translated list of twelve spheres, a translated, rotated list of five
+// boxes, a mirror ball, a glass ball and a moving sphere; `extra` adds six
+// plain spheres ("grouped_world").
+// ---------------------------------------------------------------------------
+class grouped_scene : public scene {
+public:
+    grouped_scene(double aspect, bool extra = false) : scene() {
+        auto diffuse = [](double r, double g, double b) {
+            return std::make_shared<lambertian>(std::make_shared<constant_texture>(vec3(r, g, b)));
+        };
+        typedef std::vector<std::shared_ptr<hittable>> objs;
+        Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+
+        objs balls;
+        for (int j = 0; j < 3; ++j)
+            for (int i = 0; i < 4; ++i) {
+                const int k = i + 4 * j;
+                std::shared_ptr<material> m;
+                if (k % 3 == 0)
+                    m = diffuse(0.15 + 0.07 * k, 0.8 - 0.05 * k, 0.3 + 0.04 * k);
+                else if (k % 3 == 1)
+                    m = std::make_shared<metal>(vec3(0.9 - 0.03 * k, 0.7, 0.5 + 0.04 * k), 0.05 * (k % 4));
+                else
+                    m = std::make_shared<dielectric>(1.5);
+                balls.push_back(std::make_shared<sphere>(vec3(0.8 * i, 0.3 + 0.1 * (k % 2), 0.8 * j), 0.3, m));
+            }
+        Add(std::make_shared<translate>(std::make_shared<hittable_list>(balls), vec3(-4.0, 0.0, -0.8)));
+
+        objs crates;
+        for (int k = 0; k < 5; ++k) {
+            const double x0 = 0.9 * k, z0 = 0.3 * (k % 2);
+            crates.push_back(std::make_shared<box>(vec3(x0, 0.0, z0), vec3(x0 + 0.6, 0.5 + 0.25 * k, z0 + 0.6),
+                                                   diffuse(0.75 - 0.1 * k, 0.3 + 0.1 * k, 0.25 + 0.05 * k)));
+        }
+        Add(std::make_shared<translate>(std::make_shared<rotate_y>(std::make_shared<hittable_list>(crates), 25.0),
+                                        vec3(1.6, 0.0, -1.0)));
+
+        Add(std::make_shared<sphere>(vec3(0, 1, 0), 1.0, std::make_shared<metal>(vec3(0.8, 0.8, 0.85), 0.0)));
+        Add(std::make_shared<sphere>(vec3(0.2, 0.5, 2.2), 0.5, std::make_shared<dielectric>(1.5)));
+        auto mover = std::make_shared<moving_sphere>(vec3(-1.5, 0.4, 2.4), 0.4, diffuse(0.7, 0.3, 0.1));
+        movement_linear path;
+        path.center1 = vec3(-1.5, 0.8, 2.4);
+        path.time0 = 0.0;
+        path.time1 = 1.0;
+        mover->set_movement(path);
+        Add(mover);
+
+        if (extra)
+            for (int k = 0; k < 6; ++k) {
+                const vec3 c(-3.0 + 1.2 * k, 0.25, 3.6);
+                if (k % 2 == 0)
+                    Add(std::make_shared<sphere>(c, 0.25, diffuse(0.2 + 0.1 * k, 0.4, 0.9 - 0.1 * k)));
+                else
+                    Add(std::make_shared<sphere>(c, 0.25,
+                                                 std::make_shared<metal>(vec3(0.9, 0.6 + 0.05 * k, 0.4), 0.1)));
+            }
+
+        this->cam = camera(vec3(3.0, 3.5, 10.0), vec3(0.0, 0.6, 0.0), vec3(0.0, 1.0, 0.0), 35.0, aspect, 0.0, 10.0,
+                           0.0, 1.0);
+    }
+};
+
+// "normal:<scene>": the scene with the reference's RenderType::Normal
+// (RayTracingWeekend.cpp:135-136).  render_type is a protected member with
+// no setter, so a derived class reaches it.
+struct render_type_access : scene {
+    static void set(scene* s, RenderType t) { s->*(&render_type_access::render_type) = t; }
+};
+
 static scene* make_scene(const std::string& name, double aspect) {
+    if (name.rfind("normal:", 0) == 0) {
+        scene* s = make_scene(name.substr(7), aspect);
+        render_type_access::set(s, RenderType::Normal);
+        return s;
+    }
+    if (name == "grouped") return new grouped_scene(aspect);
+    if (name == "grouped_world") return new grouped_scene(aspect, true);
     if (name == "nested") return new nested_scene(aspect);
     if (name == "nested_plain") return new nested_scene(aspect, false);
     if (name == "cornell_box") return new cornell_box_scene(aspect);

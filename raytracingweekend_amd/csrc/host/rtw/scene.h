@@ -61,6 +61,12 @@ class nested_scene : public scene {
 public:
     explicit nested_scene(double aspect, bool media = true);
 };
+// Test scene for group BVHs without media: two transformed lists (spheres,
+// boxes) among plain balls; `extra` adds plain spheres for a world BVH.
+class grouped_scene : public scene {
+public:
+    explicit grouped_scene(double aspect, bool extra = false);
+};
 
 // Test scene for image textures (not in the reference, whose scenes use
 // none): two images computed in code on every primitive kind (scenes.cpp).
@@ -74,7 +80,8 @@ public:
 };
 
 // Builds a scene by name ("cornell_box", "random_balls", "dielectric",
-// "light_sample", "book2_final", "nested", "nested_plain", "textured");
+// "light_sample", "book2_final", "nested", "nested_plain", "textured",
+// "grouped", "grouped_world");
 // nullptr for an unknown name.
 std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect);
 

@@ -339,7 +339,69 @@ textured_scene::textured_scene(double aspect, std::shared_ptr<image_texture::byt
     cam = look(vec3(0.5, 2.0, -9.0), vec3(0.0, 1.2, 0.0), 35.0, aspect, 0.0, 10.0);
 }
 
+// A test scene for group BVHs outside the media kernels (not in the
+// reference; composed the same way in oracle/ref_harness.cpp): under a
+// gradient sky, with no medium and no light list, a ground sphere, a
+// translated list of twelve spheres (lambertian, metal and glass in turn), a
+// translated, rotated list of five boxes, a mirror ball between the two
+// lists so that paths bounce from one group into the other, a glass ball and
+// a moving sphere.  Six world objects: with use_bvh the two lists get group
+// BVHs and the world stays a list.  `extra` adds six plain spheres in front
+// ("grouped_world"): twelve world objects, so a world BVH above the two
+// group BVHs.
+grouped_scene::grouped_scene(double aspect, bool extra) {
+    using list = std::vector<std::shared_ptr<hittable>>;
+    Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+
+    list balls;
+    for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < 4; ++i) {
+            const int k = i + 4 * j;
+            mat_ptr m;
+            if (k % 3 == 0)
+                m = diffuse(0.15 + 0.07 * k, 0.8 - 0.05 * k, 0.3 + 0.04 * k);
+            else if (k % 3 == 1)
+                m = std::make_shared<metal>(vec3(0.9 - 0.03 * k, 0.7, 0.5 + 0.04 * k), 0.05 * (k % 4));
+            else
+                m = std::make_shared<dielectric>(1.5);
+            balls.push_back(std::make_shared<sphere>(vec3(0.8 * i, 0.3 + 0.1 * (k % 2), 0.8 * j), 0.3, m));
+        }
+    Add(std::make_shared<translate>(std::make_shared<hittable_list>(balls), vec3(-4.0, 0.0, -0.8)));
+
+    list crates;
+    for (int k = 0; k < 5; ++k) {
+        const double x0 = 0.9 * k, z0 = 0.3 * (k % 2);
+        crates.push_back(std::make_shared<box>(vec3(x0, 0.0, z0), vec3(x0 + 0.6, 0.5 + 0.25 * k, z0 + 0.6),
+                                               diffuse(0.75 - 0.1 * k, 0.3 + 0.1 * k, 0.25 + 0.05 * k)));
+    }
+    Add(std::make_shared<translate>(std::make_shared<rotate_y>(std::make_shared<hittable_list>(crates), 25.0),
+                                    vec3(1.6, 0.0, -1.0)));
+
+    Add(std::make_shared<sphere>(vec3(0, 1, 0), 1.0, std::make_shared<metal>(vec3(0.8, 0.8, 0.85), 0.0)));
+    Add(std::make_shared<sphere>(vec3(0.2, 0.5, 2.2), 0.5, std::make_shared<dielectric>(1.5)));
+    auto mover = std::make_shared<moving_sphere>(vec3(-1.5, 0.4, 2.4), 0.4, diffuse(0.7, 0.3, 0.1));
+    movement_linear path;
+    path.center1 = vec3(-1.5, 0.8, 2.4);
+    path.time0 = 0.0;
+    path.time1 = 1.0;
+    mover->set_movement(path);
+    Add(mover);
+
+    if (extra)
+        for (int k = 0; k < 6; ++k) {
+            const vec3 c(-3.0 + 1.2 * k, 0.25, 3.6);
+            if (k % 2 == 0)
+                Add(std::make_shared<sphere>(c, 0.25, diffuse(0.2 + 0.1 * k, 0.4, 0.9 - 0.1 * k)));
+            else
+                Add(std::make_shared<sphere>(c, 0.25, std::make_shared<metal>(vec3(0.9, 0.6 + 0.05 * k, 0.4), 0.1)));
+        }
+
+    cam = look(vec3(3.0, 3.5, 10.0), vec3(0.0, 0.6, 0.0), 35.0, aspect, 0.0, 10.0);
+}
+
 std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect) {
+    if (name == "grouped") return std::make_unique<grouped_scene>(aspect);
+    if (name == "grouped_world") return std::make_unique<grouped_scene>(aspect, true);
     if (name == "nested") return std::make_unique<nested_scene>(aspect);
     if (name == "nested_plain") return std::make_unique<nested_scene>(aspect, false);
     if (name == "cornell_box") return std::make_unique<cornell_box_scene>(aspect);

@@ -8,6 +8,10 @@
 #include <vector>
 #include "rtw_host_util.h"
 
+// Items per group BVH leaf (rtw_gpu.h, rtw_bvh_node); the flattener's own cap
+// (flatten.cpp env_leaf) is the same number.
+static constexpr int kGroupLeafMax = 16;
+
 int validate_desc(const rtw_scene_desc* d) {
     if (!d) return rtw_fail(RTW_ERR_INVALID, "null scene desc");
     if (d->abi_version != RTW_ABI_VERSION) return rtw_fail(RTW_ERR_INVALID, "scene desc ABI version mismatch");
@@ -157,6 +161,15 @@ int validate_desc(const rtw_scene_desc* d) {
                     todo.push_back(N.right);
                     continue;
                 }
+                // The fp32 walk's node copy stores a group leaf as -count and
+                // reads anything below -16 as an inline pair of items
+                // (rtw_fast.h group_bvh): a larger leaf would be decoded as
+                // two item ids far outside the scene.  World leaves have no
+                // pair form, their walk reads -b as the count.
+                if (group_items && N.count > kGroupLeafMax)
+                    return rtw_fail(RTW_ERR_UNSUPPORTED,
+                                    "group BVH node " + std::to_string(n) + ": a leaf of " + std::to_string(N.count) +
+                                        " items (a group BVH leaf holds at most " + std::to_string(kGroupLeafMax) + ")");
                 for (int k = N.left; k < N.left + N.count; ++k) {
                     int it = d->bvh_items[k], span = 1;
                     if (!group_items && it < 0)

@@ -1,0 +1,211 @@
+"""Helpers of the BVH-form tests (test_bvh_forms.py on the CPU,
+test_gpu_bvh_forms.py on the GPU): reading the trees of a flattened scene
+desc, private copies of a desc with a node array of the test's own, and a
+hand-built deep world BVH.  No tests here."""
+from __future__ import annotations
+
+import ctypes as C
+
+from raytracingweekend_amd import _abi
+
+# (RTW_BVH_LEAF_MAX, RTW_BVH_WORLD_LEAF_MAX) of the leaf-form cases: leaves of
+# 3+ items (the fp32 group walk's index-and-count decode, world leaves above
+# one item), and the flattener's cap, where b == -16 is the decode's boundary
+LEAF_ENVS = [(5, 3), (16, 16)]
+GROUP_LEAF_MAX = 16  # validate_desc's limit for a group BVH leaf (rtw_gpu.h)
+STACK_MAX = 48       # rtw_scene_upload's traversal stack (rtw_device.h kStack)
+LDS_STACK = 16       # rtw_select.h kLdsStack
+
+
+def set_leaf_env(monkeypatch, leaf_max, world_leaf_max):
+    """The flattener reads both on every rtw_flatten_world call."""
+    monkeypatch.setenv("RTW_BVH_LEAF_MAX", str(leaf_max))
+    monkeypatch.setenv("RTW_BVH_WORLD_LEAF_MAX", str(world_leaf_max))
+
+
+def subtree(d, root):
+    """Node indices of the tree under `root`, the root first."""
+    out, todo = [], [root]
+    while todo:
+        n = todo.pop()
+        out.append(n)
+        if d.bvh_nodes[n].count == 0:
+            todo += [d.bvh_nodes[n].right, d.bvh_nodes[n].left]
+    return out
+
+
+def group_roots(d):
+    return [d.entries[e].bvh_root for e in range(d.n_entries) if d.entries[e].bvh_root >= 0]
+
+
+def leaf_sizes(d):
+    """(item counts of every group BVH leaf, of every world BVH leaf)."""
+    group = [d.bvh_nodes[n].count for r in group_roots(d) for n in subtree(d, r) if d.bvh_nodes[n].count > 0]
+    world = []
+    if d.world_bvh_root >= 0:
+        world = [d.bvh_nodes[n].count for n in subtree(d, d.world_bvh_root) if d.bvh_nodes[n].count > 0]
+    return group, world
+
+
+def depth(d, root):
+    best, todo = 0, [(root, 1)]
+    while todo:
+        n, k = todo.pop()
+        best = max(best, k)
+        if d.bvh_nodes[n].count == 0:
+            todo += [(d.bvh_nodes[n].left, k + 1), (d.bvh_nodes[n].right, k + 1)]
+    return best
+
+
+def stack_need(d):
+    """rtw_scene_upload's bound: world depth + deepest group depth + 2."""
+    g = max([depth(d, r) for r in group_roots(d)], default=0)
+    w = depth(d, d.world_bvh_root) if d.world_bvh_root >= 0 else 0
+    return w + g + 2
+
+
+def assert_leaf_forms(d, scene, env):
+    """The forms a leaf-form case is there for exist in this desc."""
+    group, world = leaf_sizes(d)
+    assert group or world, "no BVH at all"
+    assert max(group, default=0) <= env[0] and max(world, default=0) <= env[1]
+    if env == (5, 3):
+        assert max(group + world) >= 3, (scene, sorted(set(group)), sorted(set(world)))
+    if env == (16, 16) and scene == "book2_final":
+        assert group.count(16) >= 1, sorted(set(group))
+    if env == (16, 16) and scene == "nested_plain":
+        assert d.world_bvh_root >= 0 and d.bvh_nodes[d.world_bvh_root].count > 0
+
+
+class DescCopy:
+    """A private copy of a SceneDesc's descriptor with SceneDesc's `ptr`,
+    `desc` and `camera`, so DeviceScene and oracle_sums take it.  The arrays
+    stay the library's (the SceneDesc is kept alive) until the test replaces
+    one with its own."""
+
+    def __init__(self, sd):
+        self.base = sd
+        self._d = _abi.rtw_scene_desc.from_buffer_copy(sd.desc)
+        self.ptr = C.pointer(self._d)
+        self._keep = []
+
+    @property
+    def desc(self):
+        return self._d
+
+    @property
+    def camera(self):
+        return self._d.camera
+
+    def own_nodes(self):
+        """Replace the node array with a private copy and return it."""
+        nodes = (_abi.rtw_bvh_node * self._d.n_bvh_nodes)()
+        C.memmove(nodes, self._d.bvh_nodes, C.sizeof(nodes))
+        self._d.bvh_nodes = C.cast(nodes, C.POINTER(_abi.rtw_bvh_node))
+        self._keep.append(nodes)
+        return nodes
+
+    def set_world_bvh(self, nodes, items, root):
+        """Install a world BVH of the test's own (a desc without BVHs)."""
+        assert self._d.n_bvh_nodes == 0 and self._d.n_bvh_items == 0
+        arr = (_abi.rtw_bvh_node * len(nodes))(*nodes)
+        its = (C.c_int32 * len(items))(*items)
+        self._d.bvh_nodes = C.cast(arr, C.POINTER(_abi.rtw_bvh_node))
+        self._d.bvh_items = C.cast(its, C.POINTER(C.c_int32))
+        self._d.n_bvh_nodes, self._d.n_bvh_items, self._d.world_bvh_root = len(nodes), len(items), root
+        self._keep += [arr, its]
+
+
+def upload_status(desc):
+    """(status, message) of rtw_scene_upload of a raw desc; a handle it
+    returned is freed at once (nothing is rendered)."""
+    lib = _abi.lib()
+    h = C.c_void_p()
+    rc = lib.rtw_scene_upload(0, C.byref(desc), C.byref(h))
+    msg = (lib.rtw_last_error() or b"").decode() if rc != 0 else ""
+    if rc == 0:
+        lib.rtw_scene_free(h)
+    else:
+        assert h.value is None
+    return rc, msg
+
+
+def oversized_leaf(sd, count):
+    """A DescCopy of `sd` in which one inner group BVH node whose subtree
+    holds at least `count` items is a leaf over the first `count` of them
+    (the builder emits a subtree's items contiguously, which is checked), and
+    that node's index."""
+    d = sd.desc
+    best = None
+    for r in group_roots(d):
+        for n in subtree(d, r):
+            if d.bvh_nodes[n].count:
+                continue
+            lv = [d.bvh_nodes[k] for k in subtree(d, n) if d.bvh_nodes[k].count > 0]
+            total, first = sum(x.count for x in lv), min(x.left for x in lv)
+            assert sorted(i for x in lv for i in range(x.left, x.left + x.count)) == list(range(first, first + total))
+            if total >= count and (best is None or total < best[1]):
+                best = (n, total, first)
+    assert best is not None, "no subtree that large"
+    cp = DescCopy(sd)
+    nodes = cp.own_nodes()
+    n, _, first = best
+    nodes[n].left, nodes[n].right, nodes[n].count = first, -1, count
+    return cp, n
+
+
+def _pad(lo, hi):
+    """bvh_builder::pad_into (flatten.cpp)."""
+    m = 1e-9 * (abs(lo) + abs(hi) + (hi - lo)) + 1e-12
+    return lo - m, hi + m
+
+
+def deep_world_bvh(sd_flat, chain):
+    """A world BVH over the entries of a flat desc, from entries[i].bounds: a
+    chain that peels one entry per level for `chain` levels, then median
+    splits (longest axis of the centroids) down to one-item leaves; every
+    node's box is the union of its entries' bounds, padded as the flattener
+    pads.  Returns a DescCopy holding it."""
+    d = sd_flat.desc
+    assert d.n_bvh_nodes == 0 and d.world_bvh_root < 0 and d.n_visits == 0
+    bounds = [tuple(d.entries[i].bounds) for i in range(d.n_entries)]
+    nodes, items = [], []
+
+    def node(ids, left, right, count):
+        nd = _abi.rtw_bvh_node()
+        for a in range(3):
+            nd.bmin[a], nd.bmax[a] = _pad(min(bounds[i][a] for i in ids), max(bounds[i][3 + a] for i in ids))
+        nd.left, nd.right, nd.count, nd.pad = left, right, count, 0
+        return nd
+
+    def leaf(i):
+        me = len(nodes)
+        nodes.append(node([i], len(items), -1, 1))
+        items.append(i)
+        return me
+
+    def median(ids):
+        if len(ids) == 1:
+            return leaf(ids[0])
+        cen = [[bounds[i][a] + bounds[i][3 + a] for i in ids] for a in range(3)]
+        ax = max(range(3), key=lambda a: max(cen[a]) - min(cen[a]))
+        ids = sorted(ids, key=lambda i: bounds[i][ax] + bounds[i][3 + ax])
+        me = len(nodes)
+        nodes.append(None)
+        left, right = median(ids[:len(ids) // 2]), median(ids[len(ids) // 2:])
+        nodes[me] = node(ids, left, right, 0)
+        return me
+
+    def peel(ids, k):
+        if k == 0 or len(ids) < 2:
+            return median(ids)
+        me = len(nodes)
+        nodes.append(None)
+        left, right = leaf(ids[0]), peel(ids[1:], k - 1)
+        nodes[me] = node(ids, left, right, 0)
+        return me
+
+    root = peel(list(range(d.n_entries)), chain)
+    cp = DescCopy(sd_flat)
+    cp.set_world_bvh(nodes, items, root)
+    return cp

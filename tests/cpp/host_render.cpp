@@ -12,6 +12,7 @@
 //     out.bin: nx*ny*3 doubles (per-pixel radiance sums in sample order, row
 //     j = 0 at the bottom), then one uint64: the world traversals (hit calls)
 //
+// A scene name "normal:<name>" is <name> with RenderType::Normal (:135-136).
 // bvh: the world's objects are put under one bvh_node (the host BVH); its
 // records must equal the flat hittable_list's.
 #include <cstdint>
@@ -55,6 +56,11 @@ vec3 color(const ray& r, const scene& s, const hittable& world, int depth) {
                          color(scattered, s, world, depth - 1) / pdf_val;
 }
 
+// scene::render_type is protected and has no setter: a derived class names it
+struct render_type_access : scene {
+    static void set(scene& s, RenderType t) { s.*(&render_type_access::render_type) = t; }
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -62,7 +68,9 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: host_render <scene> <nx> <ny> <spp> <depth> <seed> <flat|bvh> <out.bin>\n");
         return 2;
     }
-    const std::string name = argv[1];
+    std::string name = argv[1];
+    const bool normal = name.rfind("normal:", 0) == 0;
+    if (normal) name = name.substr(7);
     const int nx = std::atoi(argv[2]), ny = std::atoi(argv[3]), spp = std::atoi(argv[4]), depth = std::atoi(argv[5]);
     const uint64_t seed = std::strtoull(argv[6], nullptr, 10);
     const bool bvh = std::string(argv[7]) == "bvh";
@@ -71,6 +79,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "unknown scene %s\n", name.c_str());
         return 2;
     }
+    if (normal) render_type_access::set(*sc, RenderType::Normal);
     camera& cam = sc->GetCamera();
     std::shared_ptr<hittable> tree;
     if (bvh) tree = std::make_shared<bvh_node>(sc->GetWorld().objects, cam.time0, cam.time1);

@@ -7,12 +7,14 @@
 //   2. the same descs corrupted field by field -- counts, indices, kinds,
 //      ops, BVH links, visit program, null arrays -- and handed to
 //      validate_desc, which must refuse or accept them without touching
-//      memory it does not own;
+//      memory it does not own; and Book 2 with one group BVH node turned
+//      into a leaf of 17 items (refused) and of 16 (accepted);
 //   3. refused graphs (a bvh_node over a medium, unknown subclasses, nulls);
 //   4. the oracle rendering each valid desc, finalize, the PPM writer;
 //   5. the header API's evaluating half (hit / scatter / get_ray / pdfs) over
 //      a few paths of every scene.
 // Prints "OK (<n> checks)" on success; any sanitizer report aborts.
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <cstdio>
@@ -186,7 +188,7 @@ vec3 color(const ray& r, const scene& s, int depth) {
 int main() {
     std::mt19937 g(12345);
     const char* names[] = {"cornell_box", "random_balls", "dielectric", "light_sample", "book2_final", "nested",
-                           "nested_plain"};
+                           "nested_plain", "grouped", "grouped_world"};
     char ppm[] = "/tmp/rtw_sanitize_XXXXXX";
     const int fd = mkstemp(ppm);
     CHECK(fd >= 0);
@@ -216,6 +218,38 @@ int main() {
             const vec3 c = color(r, *sc, 20);
             CHECK(c.x == c.x && c.y == c.y && c.z == c.z);
         }
+    }
+    // a group BVH leaf above 16 items (the fp32 walk would read it as an
+    // inline pair): refused; the same node with 16 items: accepted
+    {
+        setenv("RTW_BVH_LEAF_MAX", "16", 1);
+        rtw_scene_desc* d = nullptr;
+        CHECK(rtw_scene_builtin("book2_final", 1.0, 1, &d) == RTW_OK && d);
+        unsetenv("RTW_BVH_LEAF_MAX");
+        // items below every node (a subtree's items are contiguous), children first
+        std::vector<int> total(d->n_bvh_nodes, 0), first(d->n_bvh_nodes, 0);
+        auto fill = [&](auto&& self, int n) -> void {
+            const rtw_bvh_node& N = d->bvh_nodes[n];
+            if (N.count > 0) {
+                total[n] = N.count, first[n] = N.left;
+                return;
+            }
+            self(self, N.left), self(self, N.right);
+            total[n] = total[N.left] + total[N.right];
+            first[n] = std::min(first[N.left], first[N.right]);
+        };
+        int pick = -1;
+        for (int e = 0; e < d->n_entries; ++e)
+            if (d->entries[e].bvh_root >= 0) fill(fill, d->entries[e].bvh_root);
+        for (int n = 0; n < d->n_bvh_nodes; ++n)
+            if (d->bvh_nodes[n].count == 0 && total[n] >= 17 && (pick < 0 || total[n] < total[pick])) pick = n;
+        CHECK(pick >= 0);
+        for (int count : {17, 16, total[pick]}) {
+            owned_desc o(*d);
+            o.nodes[pick].left = first[pick], o.nodes[pick].right = -1, o.nodes[pick].count = count;
+            CHECK(validate_desc(&o.d) == (count > 16 ? RTW_ERR_UNSUPPORTED : RTW_OK));
+        }
+        rtw_scene_desc_free(d);
     }
     // refused graphs
     {

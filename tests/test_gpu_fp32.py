@@ -18,10 +18,14 @@ that it be indistinguishable from one:
       F(96, 96) is about 1.9)
     - bias:    |mean(d_b)| < 4 sqrt(mean(e_b^2) / 3B) + 1e-3 |image mean|
 * traversals per sample within 3 % of the fp64 mode's (same paths in law).
+
+The statistic itself lives in tests/fp32_stats.py (test_gpu_bvh_forms.py
+applies it to Normal-mode renders).
 """
 import numpy as np
 import pytest
 
+import fp32_stats
 from oracle_lib import oracle_sums
 
 pytestmark = pytest.mark.gpu
@@ -36,6 +40,9 @@ CASES = [
     ("book2_final", 64, 64, 16, 50, False),
     ("book2_final", 64, 64, 16, 50, True),
     ("nested", 48, 48, 32, 50, False),
+    # group BVHs without media: k_fast<F_GBVH> and k_fast<F_WBVH | F_GBVH>
+    ("grouped", 96, 64, 16, 50, True),
+    ("grouped_world", 96, 64, 16, 50, True),
 ]
 
 
@@ -47,37 +54,22 @@ def gpu(built):
     return render
 
 
-def blocks(acc, nx, ny, spp, b=8):
-    img = (acc / spp).reshape(ny, nx, 3)
-    return img.reshape(ny // b, b, nx // b, b, 3).mean(axis=(1, 3)).reshape(-1, 3)
-
-
 @pytest.mark.parametrize("scene,nx,ny,spp,depth,bvh", CASES,
                          ids=[f"{c[0]}{'_bvh' if c[5] else ''}" for c in CASES])
 def test_fast_mode_is_statistically_the_reference(gpu, scene, nx, ny, spp, depth, bvh):
     sd = gpu.SceneDesc(scene, nx / ny, use_bvh=bvh)
     ds = gpu.DeviceScene(sd)
     try:
-        fast = [ds.render_accumulate(nx, ny, spp, depth, seed=k, precision="fp32") for k in (0, 1, 2)]
-        other = [ds.render_accumulate(nx, ny, spp, depth, seed=k) for k in (1, 2, 3)]
+        fast, other = fp32_stats.render_sets(ds, nx, ny, spp, depth)
         info = ds.query()
     finally:
         ds.close()
-    ref, seg_ref = oracle_sums(gpu.SceneDesc(scene, nx / ny), nx, ny, spp, depth, 0)
+    ref, seg_ref = oracle_sums(gpu.SceneDesc(scene, nx / ny), nx, ny, spp, depth, fp32_stats.REF_SEED)
     for acc, st in fast:
         assert st["samples"] == nx * ny * spp and np.all(np.isfinite(acc))
         assert st["bytes_intersect"] == 36 * st["segments"]
     assert info["kernel_fast"].startswith(("k_fast<", "k_fast_sort<"))
-    rb = blocks(ref, nx, ny, spp)
-    d = np.concatenate([blocks(acc, nx, ny, spp) - rb for acc, _ in fast])
-    e = np.concatenate([blocks(acc, nx, ny, spp) - rb for acc, _ in other])
-    B = d.shape[0]
-    assert B >= 96
-    spread, base = float((d ** 2).mean()), float((e ** 2).mean())
-    assert spread < 2.0 * base, f"block spread {spread:.3e} vs fp64-noise {base:.3e}"
-    level = float(np.abs(ref).mean() / spp)
-    bias = np.abs(d.mean(axis=0))
-    assert np.all(bias < 4 * np.sqrt(base / B) + 1e-3 * level), (bias, np.sqrt(base / B))
+    fp32_stats.assert_statistically_the_reference([a for a, _ in fast], [a for a, _ in other], ref, nx, ny, spp)
     seg32 = sum(st["segments"] for _, st in fast)
     seg64 = sum(st["segments"] for _, st in other)
     assert abs(seg32 / seg64 - 1) < 0.03

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle_lib import finalize_np, oracle_sums
+from raytracingweekend_amd import _abi
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +32,11 @@ CASES = [
     ("nested", 40, 40, 3, 20, True),
     ("nested_plain", 48, 36, 4, 50, False),
     ("nested_plain", 48, 36, 4, 50, True),
+    # group BVHs without media, under a world list and under a world BVH
+    ("grouped", 48, 32, 4, 50, False),
+    ("grouped", 48, 32, 4, 50, True),
+    ("grouped_world", 48, 32, 4, 50, False),
+    ("grouped_world", 48, 32, 4, 50, True),
 ]
 
 
@@ -140,6 +146,37 @@ def test_reference_default_config_matches_committed_render(gpu):
     assert rms < 2.5, rms
 
 
+def _execution_forms_agree(gpu, monkeypatch, scene, bvh, normal=False):
+    nx, ny, spp, depth = 40, 30, 4, 50
+    sd = gpu.SceneDesc(scene, nx / ny, use_bvh=bvh)
+    if normal:
+        sd.desc.render_type = _abi.RTW_RENDER_NORMAL
+    ds = gpu.DeviceScene(sd)
+    try:
+        a, sa = ds.render_accumulate(nx, ny, spp, depth, seed=5)
+        kernels = [ds.query()["kernel"]]
+        monkeypatch.setenv("RTW_MODE", "wavefront")
+        b, sb = ds.render_accumulate(nx, ny, spp, depth, seed=5)
+        kernels.append(ds.query()["kernel"])
+        monkeypatch.setenv("RTW_SPLIT", "1")
+        c, sc = ds.render_accumulate(nx, ny, spp, depth, seed=5)
+        kernels.append(ds.query()["kernel"])
+    finally:
+        ds.close()
+    print(f"KERNELS forms {scene} bvh={bvh} normal={normal}: {kernels}")
+    assert kernels[0].startswith("k_persist") and kernels[1].startswith(("k_segment<", "k_intersect<"))
+    assert kernels[2].startswith("k_intersect<")
+    assert sa["segments"] == sb["segments"] == sc["segments"]
+    if normal:
+        assert sa["segments"] == nx * ny * spp
+    assert np.array_equal(a, b) and np.array_equal(a, c)
+    for sort in ("0", "1"):
+        d, sd_ = _render_in_child({"RTW_SORT": sort}, scene, nx, ny, spp, depth, 5, bvh, normal)
+        assert np.array_equal(a, d), f"RTW_SORT={sort}"
+        assert sd_ == sa["segments"], f"RTW_SORT={sort}"
+    return kernels
+
+
 @pytest.mark.parametrize("scene,bvh", [("cornell_box", False), ("random_balls", True), ("dielectric", False),
                                        ("nested", False)])
 def test_execution_forms_agree(gpu, monkeypatch, scene, bvh):
@@ -149,27 +186,24 @@ def test_execution_forms_agree(gpu, monkeypatch, scene, bvh):
     (k_segment; RTW_MODE=wavefront) and its split pair (k_intersect, k_shade;
     + RTW_SPLIT=1) run the same arithmetic in the same order per sample:
     bit-identical accumulators and segment counts."""
-    nx, ny, spp, depth = 40, 30, 4, 50
-    sd = gpu.SceneDesc(scene, nx / ny, use_bvh=bvh)
-    ds = gpu.DeviceScene(sd)
-    try:
-        a, sa = ds.render_accumulate(nx, ny, spp, depth, seed=5)
-        monkeypatch.setenv("RTW_MODE", "wavefront")
-        b, sb = ds.render_accumulate(nx, ny, spp, depth, seed=5)
-        monkeypatch.setenv("RTW_SPLIT", "1")
-        c, sc = ds.render_accumulate(nx, ny, spp, depth, seed=5)
-    finally:
-        ds.close()
-    assert sa["segments"] == sb["segments"] == sc["segments"]
-    assert np.array_equal(a, b) and np.array_equal(a, c)
-    for sort in ("0", "1"):
-        d = _render_in_child({"RTW_SORT": sort}, scene, nx, ny, spp, depth, 5, bvh)
-        assert np.array_equal(a, d), f"RTW_SORT={sort}"
+    _execution_forms_agree(gpu, monkeypatch, scene, bvh)
 
 
-def _render_in_child(env, scene, nx, ny, spp, depth, seed, bvh):
+@pytest.mark.parametrize("scene,bvh", [("cornell_box", False), ("grouped_world", True)])
+def test_execution_forms_agree_in_normal_mode(gpu, monkeypatch, scene, bvh):
+    """The same in RTW_RENDER_NORMAL (0.5 (n + 1) at the first hit, one
+    traversal per sample).  The render type is one of kernel selection's
+    facts (`black`), so Cornell takes other instantiations here than in
+    Shaded mode; grouped_world walks group BVHs under a world BVH in every
+    form (the split pair's k_intersect<F_WBVH | F_GBVH> included)."""
+    kernels = _execution_forms_agree(gpu, monkeypatch, scene, bvh, normal=True)
+    if scene == "grouped_world":
+        assert kernels[2] == "k_intersect<6>"  # F_WBVH | F_GBVH
+
+
+def _render_in_child(env, scene, nx, ny, spp, depth, seed, bvh, normal=False):
     """Render in a fresh process with extra environment (for switches the
-    library reads once per process)."""
+    library reads once per process).  Returns (accumulator, segments)."""
     import os
     import subprocess
     import sys
@@ -179,12 +213,15 @@ def _render_in_child(env, scene, nx, ny, spp, depth, seed, bvh):
     with tempfile.TemporaryDirectory() as td:
         out = Path(td) / "acc.npy"
         code = (f"import sys; sys.path.insert(0, {str(root)!r}); import numpy as np; "
-                f"from raytracingweekend_amd import render as r; "
-                f"ds = r.DeviceScene(r.SceneDesc({scene!r}, {nx}/{ny}, use_bvh={bvh})); "
-                f"a, _ = ds.render_accumulate({nx}, {ny}, {spp}, {depth}, seed={seed}); ds.close(); "
-                f"np.save({str(out)!r}, a)")
-        subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, check=True, timeout=300)
-        return np.load(out)
+                f"from raytracingweekend_amd import render as r, _abi; "
+                f"sd = r.SceneDesc({scene!r}, {nx}/{ny}, use_bvh={bvh}); "
+                f"sd.desc.render_type = _abi.RTW_RENDER_NORMAL if {normal} else sd.desc.render_type; "
+                f"ds = r.DeviceScene(sd); "
+                f"a, st = ds.render_accumulate({nx}, {ny}, {spp}, {depth}, seed={seed}); ds.close(); "
+                f"np.save({str(out)!r}, a); print('SEGMENTS', st['segments'])")
+        r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, check=True, timeout=300,
+                           capture_output=True, text=True)
+        return np.load(out), int(r.stdout.split("SEGMENTS")[-1].split()[0])
 
 
 def test_device_finalize_matches_host(gpu):
@@ -247,7 +284,8 @@ def test_bvh_rejects_a_wider_shutter(gpu):
         ds.close()
 
 
-@pytest.mark.parametrize("scene,nx,ny,spp", [("random_balls", 320, 200, 4), ("book2_final", 96, 96, 2)])
+@pytest.mark.parametrize("scene,nx,ny,spp", [("random_balls", 320, 200, 4), ("book2_final", 96, 96, 2),
+                                             ("grouped", 96, 64, 2), ("grouped_world", 96, 64, 2)])
 def test_bvh_equals_flat_at_size(gpu, scene, nx, ny, spp):
     """Size-independent check of the traversal shortcuts at sizes the oracle
     is too slow for: the BVH render (fp32 node bounds and slab tests,

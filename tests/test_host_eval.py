@@ -32,7 +32,7 @@ def host_render(built, tmp_path_factory):
 
 
 def render(exe, tmp_path, scene, nx, ny, spp, depth, seed, bvh=False):
-    out = tmp_path / f"{scene}_{'bvh' if bvh else 'flat'}.bin"
+    out = tmp_path / f"{scene.replace(':', '_')}_{'bvh' if bvh else 'flat'}.bin"
     r = subprocess.run([str(exe), scene, str(nx), str(ny), str(spp), str(depth), str(seed),
                         "bvh" if bvh else "flat", str(out)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
@@ -44,7 +44,10 @@ def render(exe, tmp_path, scene, nx, ny, spp, depth, seed, bvh=False):
 
 @pytest.mark.parametrize("case", CASES, ids=[c["case"] for c in CASES])
 def test_host_color_matches_reference_render(host_render, tmp_path, case):
-    sums, seg = render(host_render, tmp_path, case["scene"], case["nx"], case["ny"], case["spp"],
+    scene = case["scene"]
+    if case.get("render_type", "shaded") != "shaded":  # host_render's "normal:<scene>"
+        scene = f"{case['render_type']}:{scene}"
+    sums, seg = render(host_render, tmp_path, scene, case["nx"], case["ny"], case["spp"],
                        case["max_depth"], case["seed"])
     gold = np.load(GOLD / f"render_{case['case']}.npy")
     assert seg == case["segments"], "world traversals differ from the reference's"
@@ -54,7 +57,8 @@ def test_host_color_matches_reference_render(host_render, tmp_path, case):
 @pytest.mark.parametrize("scene,nx,ny,spp", [("random_balls", 48, 32, 2), ("cornell_box", 24, 24, 2),
                                              ("nested_plain", 24, 24, 2), ("dielectric", 32, 16, 2),
                                              ("light_sample", 32, 16, 2), ("book2_final", 16, 16, 2),
-                                             ("nested", 24, 24, 2)])
+                                             ("nested", 24, 24, 2), ("grouped", 32, 24, 2),
+                                             ("grouped_world", 32, 24, 2), ("normal:grouped_world", 32, 24, 2)])
 def test_host_bvh_equals_flat_list(host_render, tmp_path, scene, nx, ny, spp):
     """bvh_node::hit (median-split tree, nearest-first walk, then the list
     walk over the objects reaching the closest distance) picks the same

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle_lib import finalize_np, oracle, oracle_sums
+from raytracingweekend_amd import _abi
 
 GOLD = Path(__file__).resolve().parent / "golden"
 CASES = json.loads((GOLD / "renders.json").read_text())
@@ -28,6 +29,8 @@ def api(built):
 @pytest.mark.parametrize("case", CASES, ids=[c["case"] for c in CASES])
 def test_oracle_matches_reference_render(api, case):
     sd = api.SceneDesc(case["scene"], case["nx"] / case["ny"])
+    if case.get("render_type", "shaded") == "normal":  # the reference's RenderType::Normal
+        sd.desc.render_type = _abi.RTW_RENDER_NORMAL
     sums, seg = oracle_sums(sd, case["nx"], case["ny"], case["spp"], case["max_depth"], seed=case["seed"])
     gold = np.load(GOLD / f"render_{case['case']}.npy")
     assert seg == case["segments"]
