@@ -14,12 +14,12 @@
 #include "rtw_gpu.h"
 #include "rtw_div.h"
 #include "rtw_math.h"
+#include "rtw_layout.h"
 #include "rtw_select.h"
 
 #define RTW_D __device__ __forceinline__
-// vector helpers also used by the host to precompute per-primitive frames
-// with the very same arithmetic (see upload_scene)
-#define RTW_HD __host__ __device__ __forceinline__
+// (RTW_HD, and the vector helpers the host precomputes per-primitive frames
+// with in the very same arithmetic: rtw_layout.h)
 
 namespace rtwd {
 
@@ -116,18 +116,7 @@ RTW_D double log_dev(double x) {
 }
 
 // ------------------------------------------------------------------ vec3
-struct d3 {
-    double x, y, z;
-};
-RTW_HD d3 mk(double x, double y, double z) { return d3{x, y, z}; }
-RTW_HD d3 operator+(d3 a, d3 b) { return d3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-RTW_HD d3 operator-(d3 a, d3 b) { return d3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-RTW_HD d3 operator*(d3 a, d3 b) { return d3{a.x * b.x, a.y * b.y, a.z * b.z}; }
-RTW_HD d3 operator*(d3 a, double s) { return d3{a.x * s, a.y * s, a.z * s}; }
-// d3 / double (vec3.h operator/): three IEEE divisions.  (Sharing one
-// reciprocal behind a range vote measured T -3.3 %: EXPERIMENTS.md.)
-RTW_HD d3 operator/(d3 a, double s) { return d3{a.x / s, a.y / s, a.z / s}; }
-RTW_HD d3 operator-(d3 a) { return d3{-a.x, -a.y, -a.z}; }
+// (d3 and its operators, len, cross, normalize_b: rtw_layout.h)
 // a / b for a quantity that only scales radiance (RTW_RADIANCE_RCP)
 __device__ __forceinline__ double rad_div(double a, double b) {
 #if RTW_RADIANCE_RCP
@@ -136,7 +125,6 @@ __device__ __forceinline__ double rad_div(double a, double b) {
     return a / b;
 }
 RTW_HD double dot(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-RTW_HD double len2(d3 a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
 // fp64 square roots as rtw_div.h's sqrt_w (the compiler's own sequence
 // without its range scaling and class fixup, taken when the whole wave is in
 // range; bit for bit the same value) or sqrt_core where the range is known
@@ -148,16 +136,9 @@ RTW_HD double len2(d3 a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
 #define RTW_SQRT(x) __builtin_sqrt(x)
 #define RTW_SQRT_POS(x) __builtin_sqrt(x)
 #endif
-RTW_HD double len(d3 a) { return __builtin_sqrt(len2(a)); }
-RTW_HD d3 cross(d3 a, d3 b) {  // vec3.h:54-59
-    return d3{a.y * b.z - a.z * b.y, -(a.x * b.z - a.z * b.x), a.x * b.y - a.y * b.x};
-}
 // (normalize keeps the compiler's sqrt: sqrt_w's wave-uniform branch in
 // every normalization cost SGPRs, T -1.3 %)
 RTW_HD d3 normalize(d3 v) { return v / len(v); }  // vec3.h:61-67
-// (the compiler's sqrt: in onb_from_w a wave-uniform branch inside the
-// frame's normalizations turned the onb into a scratch object)
-RTW_HD d3 normalize_b(d3 v) { return v / len(v); }
 RTW_HD d3 ld3(const double* p) { return d3{p[0], p[1], p[2]}; }
 
 struct ray {
@@ -279,67 +260,11 @@ RTW_D d3 random_cosine_direction(uint32_t& s) {  // utility.h:54-67
 }
 
 // ------------------------------------------------------------------ onb
-struct onb {
-    d3 u, v, w;
-};
-// Vectors whose length is known to be about 1 are normalised
-// with rtw_div.h's bare sqrt sequence (sqrt_core: the compiler's sqrt for x
-// >= 2^-766, without its range and class handling -- no branch, no vote):
-// the second axis of every frame (cross(w, a) with w unit and |w.x| <= 0.9
-// when a = x, so |.|^2 >= 0.19 -- or >= 0.81), and frame_w of a lambertian
-// surface's normal (hit_record: (p - c) / r of a sphere, an axis normal,
-// rotated orthogonally; surf_frame::unit, a constant where shade_core builds
-// the frame -- a per-lane choice of the two forms made the frame a scratch
-// object).  A non-finite vector gives NaN either way.  T +0.25 %, C3 +0.25 %
-// (profiles/r05/ab_r5r_sqrt_unit.log).
-RTW_HD d3 normalize_unit(d3 v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return v / sqrt_core(len2(v));
-#else
-    return normalize_b(v);
-#endif
-}
-RTW_HD onb onb_from_w(d3 n) {  // onb.h:32-38
-    onb b;
-    b.w = normalize_b(n);
-    const d3 a = (fabs(b.w.x) > 0.9) ? d3{0, 1, 0} : d3{1, 0, 0};
-    b.v = normalize_unit(cross(b.w, a));
-    b.u = cross(b.w, b.v);
-    return b;
-}
+// (onb, normalize_unit, onb_from_w: rtw_layout.h)
 RTW_HD d3 local(const onb& b, d3 a) { return b.u * a.x + b.v * a.y + b.w * a.z; }  // onb.h:21-24
 
 // ------------------------------------------------------------------ scene
-// entry >= 0: one world-list entry; WORLD_RUN_PLAIN: consecutive plain
-// entries (one untransformed group each) scanned as their contiguous prims;
-// WORLD_RUN_YSPHERES: the same, all spheres for ysphere_scan.
-enum : int { WORLD_RUN_PLAIN = -1, WORLD_RUN_YSPHERES = -2 };
-struct bvh_node32;
-// Device BVH node format (rtw_scene_upload writes it, node_at reads it):
-// 32-B nodes with fp32 bounds.  (16-B fp16 nodes, twice the nodes per LDS
-// packet, measured C5 -6 %, C3 -9 %: the packet already holds every node of
-// C3 and C5 and the fp16 decode costs more; EXPERIMENTS.md.)
-using node_store = bvh_node32;
-struct world_run {
-    int32_t entry, first_prim, n_prims, movers;  // movers: the prims hold DP_MOVING_COMMON*
-};
-// Device form of a world-list entry (rtw_entry, built by the upload): the
-// header alone, its transform ops in one pool (scene::ops) -- 48 B instead of
-// the ABI's 312, so a scene's entries stay small in the LDS shading prefix
-// whatever RTW_MAX_OPS is, and op chains have no length limit here.
-struct dev_entry {
-    int32_t kind, first_prim, n_prims, n_ops;
-    int32_t first_op;     // ops [first_op, first_op + n_ops) of scene::ops, outermost first
-    int32_t phase_material, bvh_root;
-    int32_t n_outer_ops;  // MEDIUM: ops enclosing the medium (rtw_entry::n_outer_ops)
-    int32_t movers;       // the group holds DP_MOVING_COMMON* spheres
-    int32_t pad;
-    double neg_inv_density;  // MEDIUM: -(1 / density) (hittable.h:451), IEEE on the host at upload
-};
-struct dev_op {
-    int32_t type, pad;
-    double p[3];
-};
+// (world_run, dev_entry, dev_op, node_store: rtw_layout.h)
 // The media walk (scene::media) lists entry indices in visit order.
 // (A boundary cache for a medium's second visit measured C5 -8 %, and fused
 // walks of two group trees -11 %: EXPERIMENTS.md.)
@@ -445,21 +370,7 @@ RTW_D entry_v view_entry(const scene& S, int i) {
     return e;
 }
 
-// Device primitive types.  rtw_scene_upload rewrites the sphere records it
-// copies to the GPU (the caller's rtw_scene_desc is untouched), each value
-// with the reference's own expression, evaluated once instead of per test:
-//   spheres:         p[9] = radius * radius                  (sphere.h:52)
-//   moving spheres:  p[4..6] = center1 - center0, p[8] = time1 - time0
-//                                                             (sphere.h:24)
-// and moving spheres whose (time0, time1) equal the scene's common interval
-// (scene::mv_t0 / mv_den) get DP_MOVING_COMMON: their fraction
-// (time - time0) / (time1 - time0) is computed once per walk (motion_frac)
-// instead of once per sphere.  DP_MOVING_COMMON_Y: in addition
-// center1 - center0 = (0, dy, 0) and center0.x, center0.z are nonzero, so
-// center0.x + 0 * f == center0.x exactly (f is finite: upload checks the
-// interval) and only y moves.
-enum : int { DP_MOVING_COMMON = 5, DP_MOVING_COMMON_Y = 6 };
-RTW_HD bool is_sphere(int type) { return type < RTW_PRIM_RECT_XY || type > RTW_PRIM_RECT_YZ; }
+// (Device primitive types DP_MOVING_COMMON*, is_sphere: rtw_layout.h)
 
 // The moving-sphere fraction (time - time0) / (time1 - time0) of the
 // scene's common interval, computed once per walk over prims that hold
@@ -526,10 +437,6 @@ RTW_D bool rect_t(const rtw_prim& q, const ray& r, double t0, double t1, double&
 
 RTW_D bool prim_t(const rtw_prim& q, const ray& r, double t0, double t1, double& t_out, double fc) {
     return is_sphere(q.type) ? sphere_t(q, r, t0, t1, t_out, fc) : rect_t(q, r, t0, t1, t_out);
-}
-
-RTW_HD d3 rect_normal(int type) {
-    return type == RTW_PRIM_RECT_XY ? d3{0, 0, 1} : (type == RTW_PRIM_RECT_XZ ? d3{0, 1, 0} : d3{1, 0, 0});
 }
 
 // translate::hit hittable.h:299-311, rotate_y::hit :373-404 (ray inward)
@@ -774,14 +681,11 @@ RTW_D void group_scan(const scene& S, int first, int n, const ray& r, double t_m
 // with c0.y != 0, whose p[5] it sets to 0 (c0.y + 0 * fc == c0.y exactly,
 // fc finite), so one branch-free body serves the whole run: the Book-1
 // random_balls list.  Same arithmetic as sphere.h:46-81 per sphere.
-#ifndef RTW_YS_AHEAD
-#define RTW_YS_AHEAD 4
-#endif
 #ifndef RTW_YS_GROUP
 #define RTW_YS_GROUP 4  // packed pairs filtered together per iteration (2: -1.7 %, 3: -2.5 %)
 #endif
 constexpr int kYsGroup = RTW_YS_GROUP;
-constexpr int kYsAhead = RTW_YS_AHEAD;  // fp32 records in flight ahead of the filtered one
+// (kYsAhead, the fp32 records in flight ahead of the filtered one: rtw_layout.h)
 RTW_D void ysphere_scan(const scene& S, int first, int n, const ray& r, double t_min, hit_state& h, double fc) {
     const double a = dot(r.d, r.d);
     const bool oka = walk_ray_ok(S, r, fc) && div_hw_ok_b(a);  // world walk: t_min = 0.001
@@ -1037,15 +941,7 @@ RTW_D void leaf_items(const scene& S, int la, int lc, const ray& r, double t_min
     for (int k = 0; k < lc; ++k) arbitrate_item(S, S.items[la + k], r, t_min, h, fc);
 }
 
-// Device BVH node (rtw_scene_upload): the builder's padded fp64 bounds
-// rounded OUTWARD to fp32, children / leaf range in two ints.  32 B instead
-// of rtw_bvh_node's 64, and the slab test below runs in fp32 (twice the fp64
-// rate on gfx950).
-struct bvh_node32 {
-    float lo[3], hi[3];
-    int32_t a;  // inner: left child; leaf: first item
-    int32_t b;  // inner: right child | pad << 28 (push_children); leaf: -count
-};
+// (bvh_node32, the device BVH node: rtw_layout.h)
 RTW_HD int node_count(const bvh_node32& n) { return n.b < 0 ? -n.b : 0; }
 // Per-walk fp32 form of the ray for the slab tests: t = x * inv + oi per
 // axis, with oi = -o * inv moved down (oin, near planes) and up (oif, far
@@ -1108,9 +1004,8 @@ RTW_D bool slab32(const bvh_node32& nd, const slab_ray& s, float t0, float t1) {
 // BVH traversal stacks.  A private array (scratch memory) by default; the
 // persistent kernels give each lane a column of an LDS array instead (one
 // bank per lane, no scratch round trips).  Nested walks (a group BVH inside
-// a world-BVH leaf) share one stack above the outer walk's entries; the host
-// checks at upload that the deepest nesting fits (rtw_scene_upload).
-constexpr int kStack = 48;
+// a world-BVH leaf) share one stack above the outer walk's entries (kStack
+// of them, rtw_layout.h: the host checks at upload that the deepest nesting fits).
 struct local_stack {
     static constexpr int cap = kStack;
     int s[kStack];

@@ -23,7 +23,10 @@
 
 #include <cassert>
 #if defined(__HIPCC__)
-#define RTW_HD __host__ __device__ __forceinline__
+// (always-inline spelt out, not HIP's __forceinline__: hipcc compiles the host
+// library's .cpp files as HIP too, and those include no HIP header)
+#define RTW_HD __host__ __device__ inline __attribute__((always_inline))
+#define RTW_DV __device__ inline __attribute__((always_inline))
 #else
 #include <cmath>
 #include <cstdint>
@@ -119,31 +122,31 @@ RTW_HD uint32_t mod_2p31m2(uint64_t x) {
 // (a ray direction component, a vector length, a pdf) pay the quarter-rate
 // v_rcp_f64 and its refinement once.  tests/cpp/div_hw_check.hip checks the
 // identity on the card; callers keep exact a / b for lanes outside the range.
-__device__ __forceinline__ double rcp_hw(double b) {
+RTW_DV double rcp_hw(double b) {
     const double y0 = __builtin_amdgcn_rcp(b);
     const double y1 = __builtin_fma(y0, __builtin_fma(-b, y0, 1.0), y0);
     return __builtin_fma(y1, __builtin_fma(-b, y1, 1.0), y1);
 }
-__device__ __forceinline__ double div_hw(double a, double b, double y) {
+RTW_DV double div_hw(double a, double b, double y) {
     const double q = a * y;
     return __builtin_fma(__builtin_fma(-b, q, a), y, q);
 }
-__device__ __forceinline__ bool div_hw_ok_b(double b) {
+RTW_DV bool div_hw_ok_b(double b) {
     const double m = __builtin_fabs(b);
     return m >= 0x1p-200 && m <= 0x1p200;
 }
-__device__ __forceinline__ bool div_hw_ok_a(double a) {
+RTW_DV bool div_hw_ok_a(double a) {
     const double m = __builtin_fabs(a);
     return m >= 0x1p-800 && m <= 0x1p100;
 }
 // The same ranges (slightly narrower at the top: |b| < 2^200, |a| < 2^100)
 // from the biased exponent in the high word: 32-bit integer work, no 64-bit
 // constants to hold in registers.  div_hw_ok_a0 also admits a zero numerator.
-__device__ __forceinline__ uint32_t exp_bits(double v) {
+RTW_DV uint32_t exp_bits(double v) {
     return ((uint32_t)(__builtin_bit_cast(unsigned long long, v) >> 52)) & 0x7ffu;
 }
-__device__ __forceinline__ bool div_hw_ok_b_exp(double b) { return exp_bits(b) - 823u < 400u; }
-__device__ __forceinline__ bool div_hw_ok_a0_exp(double a) { return a == 0.0 || exp_bits(a) - 223u < 900u; }
+RTW_DV bool div_hw_ok_b_exp(double b) { return exp_bits(b) - 823u < 400u; }
+RTW_DV bool div_hw_ok_a0_exp(double a) { return a == 0.0 || exp_bits(a) - 223u < 900u; }
 
 // fp64 square root without the compiler's range handling.  hipcc expands
 // sqrt(x) on gfx950 as: s = x < 2^-767 ? 256 : 0; x' = ldexp(x, s); y =
@@ -152,7 +155,7 @@ __device__ __forceinline__ bool div_hw_ok_a0_exp(double a) { return a == 0.0 || 
 // the scale and fixup are identities, leaving exactly this sequence, so the
 // result is bit for bit the compiler's sqrt (tests/cpp/sqrt_check.hip on the
 // card) for 7 fewer instructions (two of them fp64 ldexp).
-__device__ __forceinline__ double sqrt_core(double x) {
+RTW_DV double sqrt_core(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y;
     double h = y * 0.5;
@@ -165,13 +168,13 @@ __device__ __forceinline__ double sqrt_core(double x) {
     return __builtin_fma(d, h, g);
 }
 // x positive, finite, >= 2^-766 (the sign and biased exponent in the high word)
-__device__ __forceinline__ bool sqrt_core_ok(double x) {
+RTW_DV bool sqrt_core_ok(double x) {
     const uint32_t hi = (uint32_t)(__builtin_bit_cast(unsigned long long, x) >> 32);
     return (hi >> 20) - 257u < 1790u;
 }
 // sqrt for a wave: the core sequence when every active lane is in its range
 // (wave-uniform branch), else the compiler's sqrt -- the same value either way
-__device__ __forceinline__ double sqrt_w(double x) {
+RTW_DV double sqrt_w(double x) {
     if (__builtin_amdgcn_ballot_w64(!sqrt_core_ok(x)) == 0) return sqrt_core(x);
     return __builtin_sqrt(x);
 }

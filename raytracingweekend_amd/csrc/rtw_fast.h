@@ -66,33 +66,7 @@ RTW_D float u01(uint32_t& s) {
 }
 
 // ------------------------------------------------------------------ scene
-// p: sphere  c0 xyz, r, c1 - c0 xyz, time0, 1 / (time1 - time0), r^2
-//    rect    lo_a, hi_a, lo_b, hi_b, k
-struct prim32 {
-    int32_t type, material, flip, entry;
-    float p[10];
-    int32_t pad[2];
-};  // 64 B
-struct ent32 {
-    int32_t kind, first_prim, n_prims, n_ops, first_op, phase_material, bvh_root, n_outer_ops;
-    float neg_inv_density;  // -1 / density (hittable.h:450)
-    int32_t pad[3];
-};  // 48 B
-struct op32 {
-    int32_t type;
-    float p[3];
-};  // 16 B
-struct mat32 {
-    int32_t type, texture;
-    float albedo[3], fuzz, ref_idx, inv_ref_idx, r0;
-    int32_t pad;
-};  // 40 B
-struct tex32 {
-    int32_t type, odd, even;  // RTW_TEX_IMAGE: odd / even = the image's nx / ny
-    float scale;
-    float color[3];
-    int32_t offset;  // RTW_TEX_IMAGE: byte offset of its first texel in fscene::texels
-};  // 32 B
+// (prim32, ent32, op32, mat32, tex32, the fp32 mirror's records: rtw_layout.h)
 
 struct fscene {
     const prim32* prims;

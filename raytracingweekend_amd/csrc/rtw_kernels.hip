@@ -23,6 +23,10 @@
 //
 // Paths are independent (the RNG is keyed by (seed, pixel, sample)), so the
 // pool order never changes a result, only its speed.
+//
+// Renders run the persistent kernels by default (k_persist_sort, k_persist,
+// k_fast_sort, k_fast below: a whole path per lane, chosen by rtw_select.h).
+// The device scene they read is laid out in host/scene_layout.cpp (records: rtw_layout.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <array>
@@ -38,6 +42,7 @@
 #include "rtw_device.h"
 #include "rtw_fast.h"
 #include "host/rtw_host_util.h"
+#include "host/scene_layout.h"
 
 using namespace rtwd;
 
@@ -737,15 +742,7 @@ __device__ __forceinline__ d3 camera_origin(const job_t& J) {
     asm volatile("" : "+s"(cp));
     return d3{ld(&cp->origin[0]), ld(&cp->origin[1]), ld(&cp->origin[2])};
 }
-// F_PIN applies to a render whose camera makes every ray at its origin: no
-// lens, no zero origin coordinate, and finite u, v (a non-finite u or v --
-// vup parallel to the view direction makes u = unit_vector(0) = NaN -- gives
-// the reference a NaN offset and NaN rays, camera.h:36-50)
-inline bool camera_is_pinhole(const rtw_camera_desc& c) {
-    bool uv = true;
-    for (int k = 0; k < 3; ++k) uv = uv && std::isfinite(c.u[k]) && std::isfinite(c.v[k]);
-    return c.lens_radius == 0.0 && c.origin[0] != 0.0 && c.origin[1] != 0.0 && c.origin[2] != 0.0 && uv;
-}
+// (camera_is_pinhole, when F_PIN applies to a render: host/scene_layout.h)
 
 // Occupancy: left alone the compiler gives k_persist 160-230 VGPRs (2-3
 // waves per SIMD).  Capping at 128 (4 waves) costs some spilled registers and
@@ -1908,18 +1905,11 @@ struct handle_t {
     int device = 0;
     hipStream_t stream = nullptr;
     scene S{};
-    bool media = false;
-    int features = 0;    // F_MEDIA | F_WBVH | F_GBVH of the uploaded scene
-    bool ysph = false;   // its world list holds y-sphere runs (F_YSPH kernels)
-    int n_runs = 0, n_ysph_runs = 0, n_plain_runs = 0;  // world-list run layout (rtw_scene_query)
-    bool movers = true;  // it holds moving spheres (else F_STATIC kernels)
-    int shade_mask = 0;  // SF_* material / texture set of the uploaded scene
+    layout_facts facts;  // what selection and rtw_scene_query read of it (host/scene_layout.h)
     const char* scene_base = nullptr;
-    uint32_t shade_bytes = 0;  // bytes of the shading prefix of scene_mem
     dev_buf scene_mem;
     dev_buf scene32;  // fp32 mirror of the scene (fast mode, rtw_fast.h)
     rtwf::fscene F32{};
-    uint32_t f32_bytes = 0;  // bytes of scene32 fp32 shading reads
     dev_buf pool[2];  // path SoA, ping-pong for compaction
     dev_buf fresh;    // staging of new camera rays (fresh_t)
     dev_buf hits;
@@ -1937,12 +1927,6 @@ struct handle_t {
     uint32_t pool_cap = 0;
     int grid = 2048;
     int cus = 256;
-    int stack_need = 0;  // deepest BVH stack a traversal of this scene can use
-    int group_depth = 0;  // depth of its deepest group BVH
-    // BVH boxes of moving spheres cover the desc camera's shutter only
-    bool bvh_motion = false;
-    double shutter0 = 0.0, shutter1 = 0.0;
-    bool desc_pin = false;  // the desc's own camera is a pinhole (F_PIN kernels; rtw_scene_query)
     std::vector<hipEvent_t> events;
 };
 
@@ -1977,632 +1961,71 @@ fresh_t carve_fresh(void* base, uint32_t cap) {
 }
 size_t fresh_bytes(uint32_t cap) { return (size_t)cap * (7 * 8 + 2 * 4); }
 
+// The scene on the card: rtw_layout_scene's two blobs (host/scene_layout.cpp)
+// copied as they are, and the kernels' scene structs pointed into them.
 int upload_scene(handle_t* h, const rtw_scene_desc* d) {
-    // one allocation, 256-byte aligned sub-arrays
-    // The media walk (scene::media, world_closest with F_MEDIA): the visit
-    // program (rtw_scene_desc::visits) without its deterministic replays --
-    // a second walk over an object with no random draws re-accepts only an
-    // exact tie -- or, without a program, the world's two walks the same way:
-    // every entry, then the media again.
-    std::vector<int32_t> media;
-    bool has_media = false;
-    for (int e = 0; e < d->n_entries; ++e) has_media |= d->entries[e].kind == RTW_ENTRY_MEDIUM;
-    if (has_media) {
-        if (d->n_visits > 0) {
-            for (int k = 0; k < d->n_visits; ++k) {
-                const int e = d->visits[k] & RTW_VISIT_ENTRY;
-                if (!(d->visits[k] & RTW_VISIT_REPLAY) || d->entries[e].kind == RTW_ENTRY_MEDIUM) media.push_back(e);
-            }
-        } else {
-            for (int e = 0; e < d->n_entries; ++e) media.push_back(e);
-            for (int e = 0; e < d->n_entries; ++e)
-                if (d->entries[e].kind == RTW_ENTRY_MEDIUM) media.push_back(e);
-        }
-    }
-    struct part {
-        const void* src;
-        size_t bytes;
-        size_t off;
-    };
-    // World-space onb of every rect primitive's normal: rect_normal, the
-    // prim's own flip, then its entry's ops outward -- hit_record's normal
-    // path (rtw_device.h) -- and onb_from_w, all with the device's expressions.
-    std::vector<double> frames((size_t)d->n_prims * 9, 0.0);
-    for (int pi = 0; pi < d->n_prims; ++pi) {
-        const rtw_prim& q = d->prims[pi];
-        if (q.type < RTW_PRIM_RECT_XY || q.entry < 0) continue;
-        d3 n = rect_normal(q.type);
-        if (q.flip & 1) n = -n;
-        const rtw_entry& e = d->entries[q.entry];
-        for (int k = RTW_MAX_OPS - 1; k >= 0; --k) {
-            if (k >= e.n_ops) continue;
-            if (e.op[k] == RTW_OP_ROTATE_Y) {
-                const double s = e.op_param[k][0], c = e.op_param[k][1];
-                const d3 n0 = n;
-                n.x = c * n0.x + s * n0.z;
-                n.z = -s * n0.x + c * n0.z;
-            } else if (e.op[k] == RTW_OP_FLIP) {
-                n = -n;
-            }
-        }
-        const onb b = onb_from_w(n);
-        double* f = frames.data() + 9 * (size_t)pi;
-        f[0] = b.u.x, f[1] = b.u.y, f[2] = b.u.z;
-        f[3] = b.v.x, f[4] = b.v.y, f[5] = b.v.z;
-        f[6] = b.w.x, f[7] = b.w.y, f[8] = b.w.z;
-    }
-    // per material: 1/ref_idx and schlick's r0^2 (material.h:158, :46-47)
-    std::vector<double> mat_aux((size_t)d->n_materials * 2, 0.0);
-    for (int k = 0; k < d->n_materials; ++k) {
-        const double ri = d->materials[k].ref_idx;
-        double r0 = (1 - ri) / (1 + ri);
-        r0 = r0 * r0;
-        mat_aux[2 * k] = 1.0 / ri;
-        mat_aux[2 * k + 1] = r0;
-    }
-    // Device copy of the prims: sphere records rewritten as rtw_device.h
-    // (DP_MOVING_COMMON) describes -- radius^2, center1 - center0, time1 -
-    // time0 precomputed with the reference's expressions -- and the moving
-    // spheres sharing the first mover's interval tagged so traversal computes
-    // their time fraction once per ray.
-    std::vector<rtw_prim> dprims(d->prims, d->prims + d->n_prims);
-    bool mv_common = false;
-    double mv_t0 = 0.0, mv_den = 1.0;
-    for (rtw_prim& q : dprims) {
-        if (!is_sphere(q.type)) continue;
-        q.p[9] = q.p[3] * q.p[3];
-        if (q.type != RTW_PRIM_MOVING_SPHERE) continue;
-        for (int k = 0; k < 3; ++k) q.p[4 + k] = q.p[4 + k] - q.p[k];
-        q.p[8] = q.p[8] - q.p[7];
-        // the shared fraction must stay finite: (time - t0) is at most ~2^129
-        // in magnitude (light pdf rays carry time FLT_MAX)
-        const bool finite_frac = std::isfinite(q.p[7]) && std::isfinite(q.p[8]) && std::fabs(q.p[8]) >= 1e-200;
-        if (!finite_frac) continue;
-        if (!mv_common) {
-            mv_common = true;
-            mv_t0 = q.p[7];
-            mv_den = q.p[8];
-        }
-        if (std::memcmp(&q.p[7], &mv_t0, 8) != 0 || std::memcmp(&q.p[8], &mv_den, 8) != 0) continue;
-        // y-only mover: x and z stay center0's exactly when dc is +-0 and
-        // center0's component is nonzero (x + +-0 == x for x != 0)
-        const bool y_only = q.p[4] == 0.0 && q.p[6] == 0.0 && q.p[0] != 0.0 && q.p[2] != 0.0;
-        q.type = y_only ? DP_MOVING_COMMON_Y : DP_MOVING_COMMON;
-    }
-    // World list runs: consecutive plain entries (one group, no BVH, no op
-    // that moves the ray -- flip_normals only turns the normal, which
-    // hit_record applies from the prim's entry) scan their contiguous prims
-    // as one run.  (Cornell: the flipped walls join the plain ones.)
-    auto ray_plain = [](const rtw_entry& E) {
-        if (E.kind != RTW_ENTRY_GROUP || E.bvh_root >= 0) return false;
-        for (int k = 0; k < E.n_ops; ++k)
-            if (E.op[k] != RTW_OP_FLIP) return false;
-        return true;
-    };
-    std::vector<world_run> runs;
-    std::vector<int32_t> entry_movers(std::max(d->n_entries, 1), 0);
-    for (int e = 0; e < d->n_entries; ++e) {
-        const rtw_entry& E = d->entries[e];
-        for (int i = E.first_prim; i < E.first_prim + E.n_prims; ++i)
-            entry_movers[e] |= dprims[i].type >= DP_MOVING_COMMON ? 1 : 0;
-        const bool plain = ray_plain(E);
-        if (plain && !runs.empty() && runs.back().entry < 0 &&
-            runs.back().first_prim + runs.back().n_prims == E.first_prim) {
-            runs.back().n_prims += E.n_prims;
-            runs.back().movers |= entry_movers[e];
-            continue;
-        }
-        runs.push_back(world_run{plain ? WORLD_RUN_PLAIN : e, E.first_prim, E.n_prims, entry_movers[e]});
-    }
-    // plain runs of y-only spheres -> ysphere_scan (static ones get dy = 0)
-    for (world_run& R : runs) {
-        if (R.entry != WORLD_RUN_PLAIN || R.n_prims < 2) continue;
-        bool all = true;
-        for (int i = R.first_prim; i < R.first_prim + R.n_prims && all; ++i)
-            all = dprims[i].type == DP_MOVING_COMMON_Y || (dprims[i].type == RTW_PRIM_SPHERE && dprims[i].p[1] != 0.0);
-        if (!all) continue;
-        R.entry = WORLD_RUN_YSPHERES;
-        for (int i = R.first_prim; i < R.first_prim + R.n_prims; ++i)
-            if (dprims[i].type == RTW_PRIM_SPHERE) dprims[i].p[5] = 0.0;
-    }
-    // ysphere_scan's fp32 prefilter records (rtw_device.h): spheres of
-    // y-sphere runs whose centre (incl. motion) is within 2^8 and radius
-    // within 2^4 are filtered, others (the random_balls ground, r = 1000)
-    // carry r^2 = +inf and always take the fp64 test; the maxima over the
-    // filtered ones bound the prefilter's rounding error
-    // (the records of a run are interleaved pairwise, spheres
-    // first + 2p and first + 2p + 1 sharing the 16 floats at 8 (first + 2p),
-    // component c of member s at 2c + s; the last sphere of a run of odd
-    // length keeps the plain record {cx, cy, cz, dy, rr} in its own 8 floats,
-    // so every record stays inside its run's slots; kYsAhead + 2 spare
-    // records at the end, slack for the unpacked form's prefetch ring)
-    std::vector<float> ysph(8 * (std::max<size_t>(dprims.size(), 1) + kYsAhead + 2), 0.0f);
-    float ysb[5] = {0, 0, 0, 0, 0};  // |cx|, |cy|, |dy|, |cz|, r^2 maxima
-    auto up = [](double v) {  // fp32 value >= v
-        float f = (float)v;
-        if ((double)f < v) f = std::nextafter(f, INFINITY);
-        return f;
-    };
-    for (const world_run& R : runs) {
-        if (R.entry != WORLD_RUN_YSPHERES) continue;
-        for (int i = R.first_prim; i < R.first_prim + R.n_prims; ++i) {
-            const rtw_prim& q = dprims[i];
-            const int k = i - R.first_prim;
-            const bool lone = k == R.n_prims - 1 && (k & 1) == 0;
-            float* const rec = ysph.data() + 8 * (size_t)(R.first_prim + (k & ~1)) + (k & 1);
-            auto f = [rec, lone](int c) -> float& { return rec[lone ? c : 2 * c]; };
-            const double dy = q.type == DP_MOVING_COMMON_Y ? q.p[5] : 0.0;
-            f(0) = (float)q.p[0], f(1) = (float)q.p[1], f(2) = (float)q.p[2], f(3) = (float)dy;
-            const bool small = std::fabs(q.p[0]) <= 256 && std::fabs(q.p[1]) <= 256 && std::fabs(dy) <= 256 &&
-                               std::fabs(q.p[2]) <= 256 && std::fabs(q.p[3]) <= 16;
-            if (!small) {
-                f(4) = INFINITY;
-                continue;
-            }
-            f(4) = (float)q.p[9];
-            ysb[0] = std::max(ysb[0], up(std::fabs(q.p[0])));
-            ysb[1] = std::max(ysb[1], up(std::fabs(q.p[1])));
-            ysb[2] = std::max(ysb[2], up(std::fabs(dy)));
-            ysb[3] = std::max(ysb[3], up(std::fabs(q.p[2])));
-            ysb[4] = std::max(ysb[4], up(q.p[9]));
-        }
-    }
-    // World-BVH leaves reference entries; a plain one-prim entry's item is
-    // replaced by ~prim so the walk tests the prim without reading the entry.
-    std::vector<int32_t> ditems(d->bvh_items, d->bvh_items + d->n_bvh_items);
-    std::vector<char> world_node(d->n_bvh_nodes, 0);  // (the fp32 nodes' inline world leaves)
-    if (d->world_bvh_root >= 0) {
-        std::vector<int> todo{d->world_bvh_root};
-        while (!todo.empty()) {
-            const rtw_bvh_node& N = d->bvh_nodes[todo.back()];
-            world_node[todo.back()] = 1;
-            todo.pop_back();
-            if (N.count == 0) {
-                todo.push_back(N.left);
-                todo.push_back(N.right);
-                continue;
-            }
-            for (int k = N.left; k < N.left + N.count; ++k) {
-                if (ditems[k] < 0 || ditems[k] >= d->n_entries)
-                    return rtw_fail(RTW_ERR_INVALID, "world bvh item out of range");
-                const rtw_entry& E = d->entries[ditems[k]];
-                if (ray_plain(E) && E.n_prims == 1)
-                    ditems[k] = ~E.first_prim;
-            }
-        }
-    }
-    // Box items' planes (scene::boxes): one 64-B record per box item,
-    // {x0, x1, y0, y1, z0, z1, first rect (int)}, packed densely (the 400
-    // ground boxes of Book 2 in 25 KB), when every box item's six rects are
-    // the hittable_list box's (+z, -z, +y, -y, +x, -x: XY at z1 and z0, XZ at
-    // y1 and y0, YZ at x1 and x0, each with the box's other two ranges) to
-    // the last bit.  The device items then read RTW_ITEM_BOX | record (the
-    // fp32 copy likewise, fscene::boxes); otherwise no table, and the walks
-    // read the rects of RTW_ITEM_BOX | first rect.
-    // (RTW_BOX_TABLE=0 at upload: no table, for tests of the rect path)
+    // (RTW_BOX_TABLE=0 at upload: no box-plane table, for tests of the rect path)
     const char* box_env = std::getenv("RTW_BOX_TABLE");
     const bool box_table = !(box_env && *box_env && std::atoi(box_env) == 0);
-    auto box_planes = [&](auto get, int i, auto* out) {  // get(prim, k) = p[k]; false if not a box
-        if (i < 0 || i + 6 > (int)dprims.size()) return false;
-        const int ty[6] = {RTW_PRIM_RECT_XY, RTW_PRIM_RECT_XY, RTW_PRIM_RECT_XZ,
-                           RTW_PRIM_RECT_XZ, RTW_PRIM_RECT_YZ, RTW_PRIM_RECT_YZ};
-        for (int j = 0; j < 6; ++j)
-            if (dprims[i + j].type != ty[j]) return false;
-        const auto x0 = get(i + 5, 4), x1 = get(i + 4, 4), y0 = get(i + 3, 4), y1 = get(i + 2, 4);
-        const auto z0 = get(i + 1, 4), z1 = get(i, 4);
-        const decltype(x0) want[6][4] = {{x0, x1, y0, y1}, {x0, x1, y0, y1}, {x0, x1, z0, z1},
-                                         {x0, x1, z0, z1}, {y0, y1, z0, z1}, {y0, y1, z0, z1}};
-        for (int j = 0; j < 6; ++j)
-            for (int k = 0; k < 4; ++k)
-                if (!(get(i + j, k) == want[j][k])) return false;
-        out[0] = x0, out[1] = x1, out[2] = y0, out[3] = y1, out[4] = z0, out[5] = z1;
-        int32_t f = i;
-        std::memcpy(out + 6, &f, sizeof f);  // the first rect, in the record's seventh slot
-        return true;
-    };
-    std::vector<int> box_firsts;  // record -> first rect
-    std::vector<double> boxes64;
-    {
-        std::vector<int> slot_items;  // item slots of box items
-        for (size_t k = 0; k < ditems.size(); ++k)
-            if (box_table && ditems[k] >= 0 && (ditems[k] & RTW_ITEM_BOX)) slot_items.push_back((int)k);
-        std::map<int, int> rec_of;
-        bool ok = true;
-        for (int k : slot_items) {
-            const int i = ditems[k] & RTW_ITEM_INDEX;
-            if (rec_of.count(i)) continue;
-            rec_of[i] = (int)box_firsts.size();
-            box_firsts.push_back(i);
-        }
-        boxes64.assign(8 * box_firsts.size(), 0.0);
-        for (size_t b = 0; b < box_firsts.size() && ok; ++b)
-            ok = box_planes([&](int q, int k) { return dprims[q].p[k]; }, box_firsts[b], boxes64.data() + 8 * b);
-        if (!ok) {
-            boxes64.clear();
-            box_firsts.clear();
-        } else {
-            for (int k : slot_items) ditems[k] = RTW_ITEM_BOX | rec_of[ditems[k] & RTW_ITEM_INDEX];
-        }
-    }
-    // Inner BVH nodes: the axis along which their children's centres differ
-    // most, and whether the left child is the upper one (push_children).
-    std::vector<rtw_bvh_node> dnodes(d->bvh_nodes, d->bvh_nodes + d->n_bvh_nodes);
-    for (rtw_bvh_node& N : dnodes) {
-        N.pad = 0;
-        if (N.count > 0) continue;
-        const rtw_bvh_node& L = d->bvh_nodes[N.left];
-        const rtw_bvh_node& R = d->bvh_nodes[N.right];
-        int ax = 0;
-        double best = -1.0;
-        for (int k = 0; k < 3; ++k) {
-            const double gap = std::fabs((R.bmin[k] + R.bmax[k]) - (L.bmin[k] + L.bmax[k]));
-            if (gap > best) best = gap, ax = k;
-        }
-        const bool left_upper = (L.bmin[ax] + L.bmax[ax]) > (R.bmin[ax] + R.bmax[ax]);
-        N.pad = ax | (left_upper ? 4 : 0);
-    }
-    // fp32 device nodes (rtw_device.h bvh_node32): bounds rounded outward;
-    // a BVH whose bounds are not finite within 2^90 is not used at all (the
-    // flat list gives the same image)
-    std::vector<bvh_node32> dnodes32(dnodes.size());
-    // The fp32 kernels' copy of the nodes: a one-item leaf holds its item
-    // (entry, ~prim, prim or box) in a instead of its index into the item
-    // array (b = -1), and a two-item group leaf holds both (a, and b =
-    // INT_MIN | second; b in [-16, -2] stays an index and a count), so the
-    // fp32 walks (rtw_fast.h) reach the prims with one dependent load less
-    // per leaf.  Measured (1 MI355X, A/B; bit-identical): C3 fp32 +1.9 %
-    // (profiles/r06/ab_r6r_C3f.log, parity_r6r_inl2.log), C5 fp32 +0.5 % for
-    // the group pairs (ab_r6t_C5f.log, parity_r6t_pair.log).  The fp64 walks
-    // keep the shared form: inline leaves there measured C3 -0.7 %
-    // (ab_r6r_C3.log).
-    std::vector<bvh_node32> dnodes32f(dnodes.size());
-    double bvh_bound = 0.0;
-    bool bvh_ok = dnodes.size() < (1u << 28);
-    for (size_t k = 0; k < dnodes.size(); ++k) {
-        const rtw_bvh_node& N = dnodes[k];
-        bvh_node32& M = dnodes32[k];
-        for (int j = 0; j < 3; ++j) {
-            bvh_ok = bvh_ok && std::isfinite(N.bmin[j]) && std::isfinite(N.bmax[j]) &&
-                     std::fabs(N.bmin[j]) <= 0x1p90 && std::fabs(N.bmax[j]) <= 0x1p90;
-            float lo = (float)N.bmin[j], hi = (float)N.bmax[j];
-            if ((double)lo > N.bmin[j]) lo = std::nextafter(lo, -INFINITY);
-            if ((double)hi < N.bmax[j]) hi = std::nextafter(hi, INFINITY);
-            M.lo[j] = lo, M.hi[j] = hi;
-            bvh_bound = std::max(bvh_bound, std::max(std::fabs((double)lo), std::fabs((double)hi)));
-        }
-        M.a = N.left;
-        M.b = N.count > 0 ? -N.count : (N.right | (N.pad << 28));
-        dnodes32f[k] = M;
-        if (N.count == 1) dnodes32f[k].a = ditems[N.left];
-        // a group leaf's two items (prims or boxes: >= 0) in a and b's low bits
-        if (!world_node[k] && N.count == 2 && ditems[N.left] >= 0 && ditems[N.left + 1] >= 0 &&
-            ditems[N.left + 1] < 0x7fffffef) {
-            dnodes32f[k].a = ditems[N.left];
-            dnodes32f[k].b = (int32_t)(0x80000000u | (uint32_t)ditems[N.left + 1]);
-        }
-    }
-    // Breadth-first numbering from all roots together (the world BVH's, then
-    // every group's, in entry order): nodes [0, k) are then the top levels of
-    // every tree, the node packet the persistent BVH kernels stage in LDS.
-    std::vector<rtw_entry> dentries(d->entries, d->entries + d->n_entries);
-    int world_root = d->world_bvh_root;
-    if (!dnodes32.empty()) {
-        std::vector<int> order, newid(dnodes32.size(), -1);
-        order.reserve(dnodes32.size());
-        auto enqueue = [&](int n) {
-            if (n >= 0 && newid[n] < 0) newid[n] = (int)order.size(), order.push_back(n);
-        };
-        enqueue(world_root);
-        for (const rtw_entry& E : dentries) enqueue(E.bvh_root);
-        for (size_t q = 0; q < order.size(); ++q) {
-            const rtw_bvh_node& N = dnodes[order[q]];
-            if (N.count == 0) enqueue(N.left), enqueue(N.right);
-        }
-        for (size_t n = 0; n < dnodes32.size(); ++n) enqueue((int)n);  // unreachable nodes keep a slot
-        auto renumber = [&](std::vector<bvh_node32>& nodes) {
-            std::vector<bvh_node32> bfs(nodes.size());
-            for (size_t n = 0; n < nodes.size(); ++n) {
-                bvh_node32 M = nodes[n];
-                if (M.b >= 0) {  // inner: renumber both children, keep the split bits
-                    M.a = newid[M.a];
-                    M.b = newid[M.b & 0x0fffffff] | (M.b & ~0x0fffffff);
-                }
-                bfs[newid[n]] = M;
-            }
-            nodes.swap(bfs);
-        };
-        renumber(dnodes32);
-        renumber(dnodes32f);
-        if (world_root >= 0) world_root = newid[world_root];
-        for (rtw_entry& E : dentries)
-            if (E.bvh_root >= 0) E.bvh_root = newid[E.bvh_root];
-    }
-    // device entries (dev_entry) and their op pool
-    std::vector<dev_entry> dev_entries(std::max<size_t>(dentries.size(), 1));
-    std::vector<dev_op> dev_ops;
-    for (size_t e = 0; e < dentries.size(); ++e) {
-        const rtw_entry& E = dentries[e];
-        dev_entry& D = dev_entries[e];
-        std::memset(&D, 0, sizeof D);
-        D.kind = E.kind, D.first_prim = E.first_prim, D.n_prims = E.n_prims, D.n_ops = E.n_ops;
-        D.first_op = (int32_t)dev_ops.size();
-        D.phase_material = E.phase_material, D.bvh_root = E.bvh_root, D.n_outer_ops = E.n_outer_ops;
-        D.movers = entry_movers[e];
-        // the reference's -(1 / density), once per upload (a correctly
-        // rounded division and a negation, as on the device)
-        D.neg_inv_density = E.kind == RTW_ENTRY_MEDIUM ? -(1.0 / E.density) : 0.0;
-        for (int k = 0; k < E.n_ops; ++k) {
-            dev_op o;
-            std::memset(&o, 0, sizeof o);
-            o.type = E.op[k];
-            for (int j = 0; j < 3; ++j) o.p[j] = E.op_param[k][j];
-            dev_ops.push_back(o);
-        }
-    }
-    std::vector<part> parts = {
-        // parts 0..10 are what shading reads; they come first so a small
-        // scene's shading data is one contiguous prefix the shade kernel can
-        // stage in LDS
-        {dprims.data(), sizeof(rtw_prim) * dprims.size(), 0},
-        {dev_entries.data(), sizeof(dev_entry) * (size_t)d->n_entries, 0},
-        {d->materials, sizeof(rtw_material) * d->n_materials, 0},
-        {d->textures, sizeof(rtw_texture) * d->n_textures, 0},
-        {d->lights, sizeof(rtw_light) * d->n_lights, 0},
-        {d->has_perlin ? d->perlin_ranvec : nullptr, d->has_perlin ? sizeof(double) * 768 : 0, 0},
-        {d->has_perlin ? d->perlin_perm : nullptr, d->has_perlin ? sizeof(int32_t) * 768 : 0, 0},
-        {media.data(), sizeof(int32_t) * media.size(), 0},
-        {frames.data(), sizeof(double) * frames.size(), 0},
-        {mat_aux.data(), sizeof(double) * mat_aux.size(), 0},
-        {dev_ops.data(), sizeof(dev_op) * dev_ops.size(), 0},
-        {dnodes32.data(), sizeof(bvh_node32) * dnodes32.size(), 0},
-        {ditems.data(), sizeof(int32_t) * ditems.size(), 0},
-        {runs.data(), sizeof(world_run) * runs.size(), 0},
-        {ysph.data(), sizeof(float) * ysph.size(), 0},
-        {boxes64.data(), sizeof(double) * boxes64.size(), 0},
-        // the image textures' texels (validate_desc: every image inside them)
-        {d->image_texels, (size_t)d->image_bytes, 0},
-    };
-    size_t total = 0;
-    for (auto& p : parts) {
-        p.off = total;
-        total += (p.bytes + 255) & ~size_t(255);
-    }
-    int rc = h->scene_mem.ensure(std::max<size_t>(total, 256));
-    if (rc) return rc;
-    std::vector<char> staging(std::max<size_t>(total, 256), 0);
-    for (auto& p : parts)
-        if (p.bytes && p.src) std::memcpy(staging.data() + p.off, p.src, p.bytes);
-    HIPCHK(hipMemcpy(h->scene_mem.p, staging.data(), staging.size(), hipMemcpyHostToDevice));
-    char* base = static_cast<char*>(h->scene_mem.p);
-    auto at = [&](int k) { return parts[k].bytes ? (void*)(base + parts[k].off) : nullptr; };
+    scene_layout L;
+    if (int rc = rtw_layout_scene(d, box_table, &L)) return rc;
+    if (int rc = h->scene_mem.ensure(L.mem64.size())) return rc;
+    if (int rc = h->scene32.ensure(L.mem32.size())) return rc;
+    HIPCHK(hipMemcpy(h->scene_mem.p, L.mem64.data(), L.mem64.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->scene32.p, L.mem32.data(), L.mem32.size(), hipMemcpyHostToDevice));
+    const char* base = static_cast<const char*>(h->scene_mem.p);
+    const char* b2 = static_cast<const char*>(h->scene32.p);
+    // an absent array is a null pointer
+    auto at = [](const char* b, const layout_span& a) { return a.bytes ? (const void*)(b + a.off) : nullptr; };
+    const layout_arrays64& A = L.at64;
+    const layout_scalars& s = L.s;
     scene& S = h->S;
-    S.prims = (const rtw_prim*)at(0);
-    S.entries = (const dev_entry*)at(1);
-    S.materials = (const rtw_material*)at(2);
-    S.textures = (const rtw_texture*)at(3);
-    S.lights = (const rtw_light*)at(4);
-    S.ranvec = (const double*)at(5);
-    S.perm = (const int32_t*)at(6);
-    S.media = (const int32_t*)at(7);
-    S.prim_onb = (const double*)at(8);
-    S.mat_aux = (const double*)at(9);
-    S.ops = (const dev_op*)at(10);
-    S.nodes = (const node_store*)at(11);
-    S.bvh_bound = bvh_bound;
-    S.items = (const int32_t*)at(12);
-    S.runs = (const world_run*)at(13);
-    S.ysph = (const float*)at(14);
-    S.boxes = (const double*)at(15);
-    S.texels = (const uint8_t*)at(16);
-    S.ysb_cx = ysb[0], S.ysb_cy = ysb[1], S.ysb_dy = ysb[2], S.ysb_cz = ysb[3], S.ysb_r2 = ysb[4];
-    S.n_runs = (int32_t)runs.size();
-    S.mv_common = mv_common ? 1 : 0;
-    S.mv_t0 = mv_t0;
-    S.mv_den = mv_den;
-    // walk_quot (rtw_device.h): every prim coordinate and radius within 2^40,
-    // every mover on the common interval
-    {
-        bool bounded = true;
-        auto in = [&](double v) { return std::isfinite(v) && std::fabs(v) <= 0x1p40; };
-        for (const rtw_prim& q : dprims) {
-            if (q.type == RTW_PRIM_MOVING_SPHERE) bounded = false;
-            const int np = is_sphere(q.type) ? (q.type == RTW_PRIM_SPHERE ? 4 : 7) : 5;
-            for (int k = 0; k < np; ++k) bounded = bounded && in(q.p[k]);
-        }
-        S.fast_div = bounded ? 1 : 0;
-    }
-    h->shade_bytes = (uint32_t)parts[11].off;  // the shading prefix
+    S.prims = (const rtw_prim*)at(base, A.prims);
+    S.entries = (const dev_entry*)at(base, A.entries);
+    S.materials = (const rtw_material*)at(base, A.materials);
+    S.textures = (const rtw_texture*)at(base, A.textures);
+    S.lights = (const rtw_light*)at(base, A.lights);
+    S.ranvec = (const double*)at(base, A.ranvec);
+    S.perm = (const int32_t*)at(base, A.perm);
+    S.media = (const int32_t*)at(base, A.media);
+    S.prim_onb = (const double*)at(base, A.prim_onb);
+    S.mat_aux = (const double*)at(base, A.mat_aux);
+    S.ops = (const dev_op*)at(base, A.ops);
+    S.nodes = (const node_store*)at(base, A.nodes);
+    S.items = (const int32_t*)at(base, A.items);
+    S.runs = (const world_run*)at(base, A.runs);
+    S.ysph = (const float*)at(base, A.ysph);
+    S.boxes = (const double*)at(base, A.boxes);
+    S.texels = (const uint8_t*)at(base, A.texels);
+    S.bvh_bound = s.bvh_bound;
+    S.ysb_cx = s.ysb_cx, S.ysb_cy = s.ysb_cy, S.ysb_dy = s.ysb_dy, S.ysb_cz = s.ysb_cz, S.ysb_r2 = s.ysb_r2;
+    S.n_runs = s.n_runs;
+    S.mv_common = s.mv_common, S.mv_t0 = s.mv_t0, S.mv_den = s.mv_den;
+    S.fast_div = s.fast_div;
+    S.n_entries = s.n_entries, S.n_lights = s.n_lights, S.light_weight = s.light_weight;
+    S.world_bvh_root = s.world_bvh_root, S.n_nodes = s.n_nodes;
+    S.render_type = s.render_type, S.background = s.background;
+    S.n_media = s.n_media, S.has_media = s.has_media;
     h->scene_base = base;
-    S.n_entries = d->n_entries;
-    S.n_lights = d->n_lights;
-    S.light_weight = d->n_lights > 0 ? 1.0 / (double)d->n_lights : 0.0;
-    S.world_bvh_root = bvh_ok ? world_root : -1;
-    S.n_nodes = bvh_ok ? (int32_t)dnodes32.size() : 0;
-    S.render_type = d->render_type;
-    S.background = d->background;
-    S.n_media = (int32_t)media.size();
-    S.has_media = has_media ? 1 : 0;
-    h->media = has_media;
-    h->features = (h->media ? F_MEDIA : 0) | (bvh_ok && d->world_bvh_root >= 0 ? F_WBVH : 0);
-    h->ysph = false;
-    for (const world_run& R : runs) h->ysph = h->ysph || R.entry == WORLD_RUN_YSPHERES;
-    h->n_runs = (int)runs.size();
-    h->n_ysph_runs = h->n_plain_runs = 0;
-    for (const world_run& R : runs) {
-        h->n_ysph_runs += R.entry == WORLD_RUN_YSPHERES;
-        h->n_plain_runs += R.entry == WORLD_RUN_PLAIN;
-    }
-    h->movers = false;
-    for (int k = 0; k < d->n_prims; ++k) h->movers = h->movers || d->prims[k].type == RTW_PRIM_MOVING_SPHERE;
-    for (int e = 0; e < d->n_entries; ++e)
-        if (bvh_ok && d->entries[e].bvh_root >= 0) h->features |= F_GBVH;
-    int m = 0;
-    for (int k = 0; k < d->n_materials; ++k) {
-        const int t = d->materials[k].type;
-        m |= t == RTW_MAT_METAL ? SF_METAL : t == RTW_MAT_DIELECTRIC ? SF_DIEL : t == RTW_MAT_ISOTROPIC ? SF_ISO : 0;
-    }
-    for (int k = 0; k < d->n_textures; ++k) {
-        const int t = d->textures[k].type;
-        m |= t == RTW_TEX_NOISE ? SF_NOISE : t == RTW_TEX_CHECKER ? SF_CHECKER : t == RTW_TEX_IMAGE ? SF_IMAGE : 0;
-    }
-    h->shade_mask = m;
-    // BVH stack depth: a walk pushes two children per inner node and pops
-    // one, so it holds at most depth + 1 entries; a group BVH inside a world
-    // leaf stacks on top of the world walk
-    auto depth = [&](int root) {
-        int best = 0;
-        std::vector<std::pair<int, int>> todo{{root, 1}};
-        while (!todo.empty()) {
-            const auto [n, dd] = todo.back();
-            todo.pop_back();
-            best = std::max(best, dd);
-            const rtw_bvh_node& N = d->bvh_nodes[n];
-            if (N.count == 0) todo.push_back({N.left, dd + 1}), todo.push_back({N.right, dd + 1});
-        }
-        return best;
-    };
-    int group_depth = 0;
-    for (int e = 0; e < d->n_entries; ++e)
-        if (d->entries[e].bvh_root >= 0) group_depth = std::max(group_depth, depth(d->entries[e].bvh_root));
-    const int world_depth = d->world_bvh_root >= 0 ? depth(d->world_bvh_root) : 0;
-    h->stack_need = world_depth + group_depth + 2;
-    // A walk from an empty stack that pops one node and pushes both children
-    // of an inner one holds at most D entries for a tree of depth D (the
-    // entry at stack position j has depth >= j + 1: true for the root at 0,
-    // and an inner node of depth k popped from position k' <= k - 1 puts
-    // depth-(k + 1) children at k' and k' + 1).  The fp32 media kernel's
-    // group walks are such walks (select_fp32).
-    h->group_depth = group_depth;
-    bool movers = false;
-    for (int k = 0; k < d->n_prims; ++k) movers |= d->prims[k].type == RTW_PRIM_MOVING_SPHERE;
-    h->desc_pin = camera_is_pinhole(d->camera);
-    h->bvh_motion = movers && d->n_bvh_nodes > 0;
-    h->shutter0 = std::min(d->camera.time0, d->camera.time1);
-    h->shutter1 = std::max(d->camera.time0, d->camera.time1);
-    if (h->stack_need > kStack)
-        return rtw_fail(RTW_ERR_UNSUPPORTED, "BVH too deep for the traversal stack (" + std::to_string(h->stack_need) +
-                                                 " > " + std::to_string(kStack) + " entries)");
-
-    // fp32 mirror for the fast mode (rtw_fast.h): prims, entries, ops,
-    // materials, textures, Perlin vectors and rect frames in single
-    // precision; BVH nodes / items, world runs, the media walk and the lights
-    // are the arrays above
-    {
-        using namespace rtwf;
-        std::vector<prim32> p32(std::max(d->n_prims, 1));
-        for (int i = 0; i < d->n_prims; ++i) {
-            const rtw_prim& q = d->prims[i];
-            prim32& o = p32[i];
-            std::memset(&o, 0, sizeof o);
-            o.type = q.type, o.material = q.material, o.flip = q.flip, o.entry = q.entry;
-            for (int k = 0; k < 10; ++k) o.p[k] = (float)q.p[k];
-            if (is_sphere(q.type)) {
-                o.p[9] = (float)(q.p[3] * q.p[3]);
-                if (q.type == RTW_PRIM_MOVING_SPHERE) {
-                    for (int k = 0; k < 3; ++k) o.p[4 + k] = (float)(q.p[4 + k] - q.p[k]);
-                    o.p[7] = (float)q.p[7];
-                    o.p[8] = (float)(1.0 / (q.p[8] - q.p[7]));
-                }
-            }
-        }
-        std::vector<ent32> e32(std::max(d->n_entries, 1));
-        for (int e = 0; e < d->n_entries; ++e) {
-            const dev_entry& D = dev_entries[e];
-            ent32& o = e32[e];
-            std::memset(&o, 0, sizeof o);
-            o.kind = D.kind, o.first_prim = D.first_prim, o.n_prims = D.n_prims, o.n_ops = D.n_ops;
-            o.first_op = D.first_op, o.phase_material = D.phase_material;
-            o.bvh_root = bvh_ok ? D.bvh_root : -1;
-            o.n_outer_ops = D.n_outer_ops;
-            o.neg_inv_density = (float)D.neg_inv_density;
-        }
-        std::vector<op32> o32(std::max<size_t>(dev_ops.size(), 1));
-        for (size_t k = 0; k < dev_ops.size(); ++k) {
-            o32[k].type = dev_ops[k].type;
-            for (int j = 0; j < 3; ++j) o32[k].p[j] = (float)dev_ops[k].p[j];
-        }
-        std::vector<mat32> m32(std::max(d->n_materials, 1));
-        for (int k = 0; k < d->n_materials; ++k) {
-            const rtw_material& M = d->materials[k];
-            mat32& o = m32[k];
-            std::memset(&o, 0, sizeof o);
-            o.type = M.type, o.texture = M.texture;
-            for (int j = 0; j < 3; ++j) o.albedo[j] = (float)M.albedo[j];
-            o.fuzz = (float)M.fuzz, o.ref_idx = (float)M.ref_idx;
-            o.inv_ref_idx = (float)mat_aux[2 * k], o.r0 = (float)mat_aux[2 * k + 1];
-        }
-        std::vector<tex32> t32(std::max(d->n_textures, 1));
-        for (int k = 0; k < d->n_textures; ++k) {
-            const rtw_texture& T = d->textures[k];
-            tex32& o = t32[k];
-            std::memset(&o, 0, sizeof o);
-            o.type = T.type, o.odd = T.odd, o.even = T.even, o.scale = (float)T.scale;
-            o.offset = T.offset;  // RTW_TEX_IMAGE: odd / even = nx / ny, texels at S.texels + offset
-            for (int j = 0; j < 3; ++j) o.color[j] = (float)T.color[j];
-        }
-        std::vector<float> boxes32(8 * box_firsts.size(), 0.0f);  // the same records in fp32 (fscene::boxes)
-        for (size_t b = 0; b < box_firsts.size(); ++b)
-            if (!box_planes([&](int q, int k) { return p32[q].p[k]; }, box_firsts[b], boxes32.data() + 8 * b))
-                return rtw_fail(RTW_ERR_INVALID, "box planes: fp32 rects differ from the fp64 ones");
-        std::vector<float> rv32(d->has_perlin ? 768 : 0), fr32(frames.size());
-        for (size_t k = 0; k < rv32.size(); ++k) rv32[k] = (float)d->perlin_ranvec[k];
-        for (size_t k = 0; k < frames.size(); ++k) fr32[k] = (float)frames[k];
-        // everything fp32 shading reads, in one allocation: the prefix the
-        // regrouping kernel stages in LDS (k_fast_sort)
-        std::vector<part> p2 = {
-            {p32.data(), sizeof(prim32) * p32.size(), 0},
-            {e32.data(), sizeof(ent32) * e32.size(), 0},
-            {o32.data(), sizeof(op32) * o32.size(), 0},
-            {m32.data(), sizeof(mat32) * m32.size(), 0},
-            {t32.data(), sizeof(tex32) * t32.size(), 0},
-            {rv32.data(), sizeof(float) * rv32.size(), 0},
-            {fr32.data(), sizeof(float) * fr32.size(), 0},
-            {d->lights, sizeof(rtw_light) * d->n_lights, 0},
-            {d->has_perlin ? d->perlin_perm : nullptr, d->has_perlin ? sizeof(int32_t) * 768 : 0, 0},
-            // (after the staged prefix)
-            {dnodes32f.data(), sizeof(bvh_node32) * dnodes32f.size(), 0},
-            {boxes32.data(), sizeof(float) * boxes32.size(), 0},
-        };
-        size_t tot = 0;
-        for (auto& x : p2) {
-            x.off = tot;
-            tot += (x.bytes + 255) & ~size_t(255);
-        }
-        if ((rc = h->scene32.ensure(std::max<size_t>(tot, 256)))) return rc;
-        std::vector<char> st2(std::max<size_t>(tot, 256), 0);
-        for (auto& x : p2)
-            if (x.bytes && x.src) std::memcpy(st2.data() + x.off, x.src, x.bytes);
-        HIPCHK(hipMemcpy(h->scene32.p, st2.data(), st2.size(), hipMemcpyHostToDevice));
-        char* b2 = static_cast<char*>(h->scene32.p);
-        fscene& F = h->F32;
-        F.prims = (const prim32*)(b2 + p2[0].off);
-        F.entries = (const ent32*)(b2 + p2[1].off);
-        F.ops = (const op32*)(b2 + p2[2].off);
-        F.materials = (const mat32*)(b2 + p2[3].off);
-        F.textures = (const tex32*)(b2 + p2[4].off);
-        F.ranvec = p2[5].bytes ? (const float*)(b2 + p2[5].off) : nullptr;
-        F.frames = (const float*)(b2 + p2[6].off);
-        F.lights = p2[7].bytes ? (const rtw_light*)(b2 + p2[7].off) : nullptr;
-        F.perm = p2[8].bytes ? (const int32_t*)(b2 + p2[8].off) : nullptr;
-        h->f32_bytes = (uint32_t)(p2[8].off + p2[8].bytes);
-        F.nodes = S.nodes ? (const node_store*)(b2 + p2[9].off) : nullptr;
-        F.boxes = p2[10].bytes ? (const float*)(b2 + p2[10].off) : nullptr;
-        F.texels = S.texels;
-        F.items = S.items;
-        F.runs = S.runs;
-        F.media = S.media;
-        F.ysph = S.ysph;
-        F.mv_t0 = (float)S.mv_t0;
-        F.mv_inv_den = (float)(1.0 / S.mv_den);
-        F.light_weight = (float)S.light_weight;
-        F.n_lights = S.n_lights;
-        F.world_bvh_root = S.world_bvh_root;
-        F.render_type = S.render_type;
-        F.background = S.background;
-        F.n_media = S.n_media;
-        F.n_runs = S.n_runs;
-        F.n_nodes = S.n_nodes;
-    }
+    const layout_arrays32& B = L.at32;
+    rtwf::fscene& F = h->F32;
+    F.prims = (const rtwf::prim32*)at(b2, B.prims);
+    F.entries = (const rtwf::ent32*)at(b2, B.entries);
+    F.ops = (const rtwf::op32*)at(b2, B.ops);
+    F.materials = (const rtwf::mat32*)at(b2, B.materials);
+    F.textures = (const rtwf::tex32*)at(b2, B.textures);
+    F.ranvec = (const float*)at(b2, B.ranvec);
+    F.frames = (const float*)(b2 + B.frames.off);  // (never null, prims or not)
+    F.lights = (const rtw_light*)at(b2, B.lights);
+    F.perm = (const int32_t*)at(b2, B.perm);
+    F.nodes = (const node_store*)at(b2, B.nodes);
+    F.boxes = (const float*)at(b2, B.boxes);
+    F.texels = S.texels, F.items = S.items, F.runs = S.runs, F.media = S.media, F.ysph = S.ysph;
+    F.mv_t0 = s.f_mv_t0, F.mv_inv_den = s.f_mv_inv_den, F.light_weight = s.f_light_weight;
+    F.n_lights = S.n_lights, F.world_bvh_root = S.world_bvh_root;
+    F.render_type = S.render_type, F.background = S.background;
+    F.n_media = S.n_media, F.n_runs = S.n_runs, F.n_nodes = S.n_nodes;
+    h->facts = L.facts;
     return RTW_OK;
 }
 
@@ -2727,13 +2150,7 @@ select_env read_env() {
 
 // What selection reads of an uploaded scene; pin: the camera is a pinhole.
 select_in scene_facts(const handle_t* h, bool pin) {
-    select_in s;
-    s.features = h->features, s.shade_mask = h->shade_mask;
-    s.shade_bytes = h->shade_bytes, s.f32_bytes = h->f32_bytes;
-    s.stack_need = h->stack_need, s.group_depth = h->group_depth, s.n_nodes = h->S.n_nodes;
-    s.ysph = h->ysph, s.static_scene = !h->movers, s.lights = h->S.n_lights > 0;
-    s.black = h->S.background != RTW_BG_GRADIENT && h->S.render_type != RTW_RENDER_NORMAL;
-    s.pin = pin;
+    select_in s = rtw_layout_select_in(h->facts, pin);
     s.strict = RTW_STRICT_RADIANCE != 0;
     return s;
 }
@@ -2741,8 +2158,8 @@ select_in scene_facts(const handle_t* h, bool pin) {
 // fp32 renders of a scene with image textures exist for list and world-BVH
 // scenes (select_fp32); media or group BVHs with images: fp64 only.
 bool fast_image_ok(const handle_t* h) {
-    const int f = h->features & (F_MEDIA | F_WBVH | F_GBVH);
-    return !(h->shade_mask & SF_IMAGE) || f == 0 || f == F_WBVH;
+    const int f = h->facts.features & (F_MEDIA | F_WBVH | F_GBVH);
+    return !(h->facts.shade_mask & SF_IMAGE) || f == 0 || f == F_WBVH;
 }
 
 // A render's kernel under the current environment: the choice, its row of the
@@ -2758,7 +2175,7 @@ int plan_render(const handle_t* h, bool pin, bool fast, plan_t* out) {
     s.env = read_env();
     plan_t p{fast ? select_fp32(s) : select_fp64(s)};
     const inst& id = p.c.id;
-    p.shm = !id.l ? 0 : p.c.form == kform::fast_sort ? h->f32_bytes : p.c.form == kform::fast ? 0 : h->shade_bytes;
+    p.shm = !id.l ? 0 : p.c.form == kform::fast_sort ? h->facts.f32_bytes : p.c.form == kform::fast ? 0 : h->facts.shade_bytes;
     const kform form = p.c.form;
     const bool fp64 = form == kform::persist_sort || form == kform::persist || form == kform::persist_lst;
     const int at = fp64 ? index_of(kPersistList, id) : form == kform::segment ? index_of(kSegmentList, id)
@@ -2784,7 +2201,7 @@ int plan_render(const handle_t* h, bool pin, bool fast, plan_t* out) {
 // One pass of a persistent plan (FA: the fp32 kernels' arguments).
 void launch_persistent(const plan_t& p, const handle_t* h, hipStream_t st, const job_t& J, ctrs_t* C,
                        const fast_args& FA) {
-    const persist_args PA{h->S, J, C, h->scene_base, h->shade_bytes};
+    const persist_args PA{h->S, J, C, h->scene_base, h->facts.shade_bytes};
     switch (p.c.form) {
     case kform::persist_sort:
         launch(p.fn, grid_blocks(p.fn, kSortBlock, p.shm, h->cus), kSortBlock, p.shm, st, PA);
@@ -2810,7 +2227,7 @@ void launch_persistent(const plan_t& p, const handle_t* h, hipStream_t st, const
     }
     case kform::fast_sort: {
         const char* base = static_cast<const char*>(h->scene32.p);
-        const uint32_t bytes = h->f32_bytes;
+        const uint32_t bytes = h->facts.f32_bytes;
         fast_args a = FA;  // the arrays' offsets in the LDS copy (lds_fscene_off)
         const void* ptrs[9] = {FA.S.prims, FA.S.entries, FA.S.ops, FA.S.materials, FA.S.textures,
                                FA.S.lights, FA.S.ranvec, FA.S.perm, FA.S.frames};
@@ -2919,17 +2336,17 @@ extern "C" int rtw_scene_query(void* handle, rtw_scene_info* out) {
     if (!h || !out) return rtw_fail(RTW_ERR_INVALID, "rtw_scene_query: null argument");
     std::memset(out, 0, sizeof *out);
     out->device = h->device;
-    out->n_world_runs = h->n_runs;
-    out->n_ysphere_runs = h->n_ysph_runs;
-    out->n_plain_runs = h->n_plain_runs;
-    out->features = h->features;
-    out->shade_mask = h->shade_mask;
-    out->shade_lds_bytes = h->shade_bytes <= kShadeLdsMax ? (int32_t)h->shade_bytes : 0;
+    out->n_world_runs = h->facts.n_runs;
+    out->n_ysphere_runs = h->facts.n_ysph_runs;
+    out->n_plain_runs = h->facts.n_plain_runs;
+    out->features = h->facts.features;
+    out->shade_mask = h->facts.shade_mask;
+    out->shade_lds_bytes = h->facts.shade_bytes <= kShadeLdsMax ? (int32_t)h->facts.shade_bytes : 0;
     HIPCHK(hipSetDevice(h->device));  // occupancy queries of the plans
     // the kernels of a render with the scene's own camera
     plan_t p64, p32;
-    if (int rc = plan_render(h, h->desc_pin, false, &p64)) return rc;
-    if (int rc = plan_render(h, h->desc_pin, true, &p32)) return rc;
+    if (int rc = plan_render(h, h->facts.desc_pin, false, &p64)) return rc;
+    if (int rc = plan_render(h, h->facts.desc_pin, true, &p32)) return rc;
     out->bvh_lds_nodes = (int32_t)p64.packet;
     std::snprintf(out->kernel, sizeof out->kernel, "%s", p64.c.name.c_str());
     std::snprintf(out->build_id, sizeof out->build_id, "%s", RTW_BUILD_ID);
@@ -3102,14 +2519,14 @@ int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, wave_pool& W
         if (it > cap) return rtw_fail(RTW_ERR_HIP, "wavefront did not drain (internal error)");
         if (plan.c.form == kform::segment) {
             rc = timed(time_isect, [&] {
-                launch(plan.fn, grid, kBlock, plan.shm, st, h->S, J, W.A, W.FR, C, h->scene_base, h->shade_bytes);
+                launch(plan.fn, grid, kBlock, plan.shm, st, h->S, J, W.A, W.FR, C, h->scene_base, h->facts.shade_bytes);
             });
             if (rc) return rc;
         } else {
             rc = timed(time_isect, [&] { launch_intersect(plan, grid, st, h->S, W.A, W.FR, W.ht, W.hid, C); });
             if (rc) return rc;
             rc = timed(time_shade, [&] {
-                launch_shade(plan, grid, st, h->S, J, W.A, W.FR, W.ht, W.hid, C, h->scene_base, h->shade_bytes);
+                launch_shade(plan, grid, st, h->S, J, W.A, W.FR, W.ht, W.hid, C, h->scene_base, h->facts.shade_bytes);
             });
             if (rc) return rc;
         }
@@ -3162,8 +2579,8 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
     const uint64_t npix = (uint64_t)n_rows * (uint64_t)R.nx;
     if ((uint64_t)R.nx * R.ny >= (1ull << 32) || npix >= (1ull << 31))
         return rtw_fail(RTW_ERR_INVALID, "image too large for 32-bit pixel ids");
-    if (h->bvh_motion && (std::min(camera->time0, camera->time1) < h->shutter0 ||
-                          std::max(camera->time0, camera->time1) > h->shutter1))
+    if (h->facts.bvh_motion && (std::min(camera->time0, camera->time1) < h->facts.shutter0 ||
+                          std::max(camera->time0, camera->time1) > h->facts.shutter1))
         return rtw_fail(RTW_ERR_INVALID,
                         "rtw_render_accumulate: camera shutter outside the one the scene's BVH was built for "
                         "(moving spheres); flatten the scene with this camera");

@@ -4,7 +4,7 @@
 
 #include <stdint.h>
 #if defined(__HIPCC__)
-#define RTW_HD __host__ __device__ __forceinline__
+#define RTW_HD __host__ __device__ inline __attribute__((always_inline))  // (as rtw_div.h)
 #else
 #include <cmath>
 #define RTW_HD inline
