@@ -41,6 +41,7 @@
 #include <vector>
 #include "rtw_device.h"
 #include "rtw_fast.h"
+#include "rtw_queue.h"
 #include "host/rtw_host_util.h"
 #include "host/scene_layout.h"
 
@@ -69,40 +70,6 @@ struct fresh_t {  // staging of new camera rays, indexed like the pool
     double *ox, *oy, *oz, *dx, *dy, *dz, *tm;
     uint32_t *rng, *qid;
 };
-
-// The sample queue is sharded over kQShards counters to spread the atomics:
-// shard s owns the chunks c = s, s + kQShards, ... of kQChunk consecutive
-// samples, and its j-th sample is  q = ((j / kQChunk) * kQShards + s) * kQChunk
-// + j % kQChunk.
-constexpr int kQShards = 8;
-constexpr uint32_t kQChunk = 1024;
-
-// Counters hit by many workgroups live on 256-byte lines of their own: all
-// words of one line are served by one L2 channel, which serialises them
-// (one word saturates at ~88 atomics/us).  Shard k is used by the blocks with
-// blockIdx % 8 == k, i.e. by one XCD.
-struct alignas(256) ctr_line {
-    unsigned long long v;
-    unsigned long long pad[31];
-};
-
-struct ctrs_t {
-    ctr_line qshard[kQShards];  // per-shard count of samples handed out
-    ctr_line segments[8];       // world hit queries (live paths intersected)
-    unsigned int n;                      // slots in the current pool
-    unsigned int n_out;                  // compaction output count
-    unsigned int pad[4];
-};
-
-__host__ __device__ inline uint64_t shard_sample(int s, uint64_t j) {
-    return ((j / kQChunk) * kQShards + (uint64_t)s) * kQChunk + j % kQChunk;
-}
-// number of the pass's `total` samples that shard s owns (its ids 0..limit-1)
-__host__ __device__ inline uint64_t shard_limit(int s, uint64_t total) {
-    const uint64_t full = total / kQChunk, rem = total % kQChunk;
-    const uint64_t nfull = full > (uint64_t)s ? (full - (uint64_t)s + kQShards - 1) / kQShards : 0;
-    return nfull * kQChunk + ((full % kQShards) == (uint64_t)s ? rem : 0);
-}
 
 struct job_t {
     const rtw_camera_desc* cam;  // device copy (read where rays are made, see camera_sample)
@@ -197,6 +164,17 @@ __device__ __forceinline__ ray camera_sample(const job_t& J, uint32_t q, uint32_
                           : (c.lens_radius == 0.0 && c.origin[0] != 0.0 && c.origin[1] != 0.0 && c.origin[2] != 0.0);
     return camera_ray(c, u, v, rng, pin);
 }
+// ... and of the fp32 fast mode (rtw_fast.h): the same sample decomposition
+// and engine, single-precision jitter and camera
+__device__ __forceinline__ rtwf::fray camera_sample_f32(const job_t& J, const rtwf::cam32& cam, uint32_t q,
+                                                        uint32_t& rng) {
+    int i, j, s;
+    sample_coords(J, q, i, j, s);
+    rng = path_seed(J.seed_mix, (uint32_t)(j * J.nx + i), (uint32_t)s);
+    const float u = ((float)i + rtwf::u01(rng)) * rtwf::rcp((float)J.nx);
+    const float v = ((float)j + rtwf::u01(rng)) * rtwf::rcp((float)J.ny);
+    return rtwf::camera_ray(cam, u, v, rng);
+}
 
 __device__ __forceinline__ void raygen(const job_t& J, const fresh_t& F, uint32_t k, uint32_t q) {
     uint32_t rng;
@@ -268,6 +246,32 @@ __device__ __forceinline__ uint32_t block_rank(bool flag, uint32_t* s_wave, uint
     }
     total = tot;
     return before + (uint32_t)__popcll(m & lanemask_lt());
+}
+
+// Two steps the persistent kernels share.  (The wavefront kernels spell them
+// out: through these functions k_intersect, k_segment and k_shade compile to
+// other instruction orders, and nothing times those kernels.)
+// Copy n16 16-byte units from src into LDS, the block's `block` threads
+// striding over them (the caller's barrier follows).
+__device__ __forceinline__ void stage_lds(char* lds, const void* src, uint32_t n16, uint32_t block) {
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    uint4* d = reinterpret_cast<uint4*>(lds);
+    for (uint32_t k = threadIdx.x; k < n16; k += block) d[k] = s[k];
+}
+// The segment counter: every lane's count of world hit queries, folded per
+// wave into s_cnt[WAVES], then one 64-bit atomic per block.  ctrs() gives the
+// counters where thread 0 adds to them: the kernels load the pointer there
+// (loaded before the barrier it cost k_fast<2, true> a spilled VGPR).
+template <int WAVES, class Ctrs>
+__device__ __forceinline__ void count_segments(uint32_t segs, uint32_t* s_cnt, Ctrs ctrs) {
+    for (int off = 32; off > 0; off >>= 1) segs += __shfl_down(segs, off, 64);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = segs;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (int k = 0; k < WAVES; ++k) t += s_cnt[k];
+        if (t) atomicAdd(&ctrs()->segments[blockIdx.x % 8].v, t);
+    }
 }
 
 // One world closest-hit query per live path.  The next path's ray is loaded
@@ -781,6 +785,49 @@ __device__ __forceinline__ const persist_args& args_now() {
     return *(const persist_args*)p;
 }
 
+// A wave's reservation on the sample queue (rtw_queue.h): the wave takes one
+// id of the pass's `total` for each lane of the ballot `takers` (this lane is
+// one of them when `takes`), its block's own shard first, then the others in
+// turn (a dry shard is skipped without an atomic).  Lane 0 does the atomics
+// and broadcasts each base; the takers get the ids of each grant in lane order.
+// k_fast and k_fast_sort call this.  k_persist and k_persist_sort spell the
+// same loop out (through the function they measured slower,
+// profiles/persist_shared/ab_parent_vs_shared.txt): a change to the queue is
+// made here, in those two kernels, and in k_regen's block-level form.
+struct reservation {
+    uint32_t q;  // this lane's sample id (got)
+    bool got;    // this lane holds an id
+    bool open;   // the wave got all it wanted: the queue may hold more
+};
+__device__ __forceinline__ reservation reserve_samples(ctrs_t* C, uint32_t total, unsigned long long takers,
+                                                       bool takes) {
+    const int own = blockIdx.x % kQShards;
+    const bool lead = (threadIdx.x & 63) == 0;
+    const uint32_t rank = (uint32_t)__popcll(takers & lanemask_lt());
+    uint32_t left = (uint32_t)__popcll(takers), given = 0, q = 0;
+    bool got = false;
+    for (int a = 0; a < kQShards && left; ++a) {
+        const int sh = (own + a) % kQShards;
+        const unsigned long long lim = shard_limit(sh, total);
+        unsigned long long b = ~0ull;
+        if (lead) {
+            const bool dry = a > 0 && __hip_atomic_load(&C->qshard[sh].v, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT) >= lim;
+            if (!dry) b = atomicAdd(&C->qshard[sh].v, (unsigned long long)left);
+        }
+        b = __shfl(b, 0, 64);
+        if (b == ~0ull || b >= lim) continue;
+        const uint32_t ok = (uint32_t)min((unsigned long long)left, lim - b);
+        if (takes && rank >= given && rank < given + ok) {
+            q = (uint32_t)shard_sample(sh, b + (rank - given));
+            got = true;
+        }
+        given += ok;
+        left -= ok;
+    }
+    return reservation{q, got, left == 0};
+}
+
 // LST: BVH traversal stacks in LDS (one column per lane) instead of scratch.
 // The loop-carried ray stays in registers: every form that parked it in LDS
 // (the whole ray with lane-direct camera samples, or its origin beside
@@ -799,19 +846,14 @@ void k_persist(persist_args) {
     __shared__ uint32_t s_q[kPBlock];     // each lane's sample id
     if (LDS) {
         const persist_args& A = args_now();
-        const uint4* src = reinterpret_cast<const uint4*>(A.base);
-        uint4* dst = reinterpret_cast<uint4*>(s_scene);
-        for (uint32_t k = threadIdx.x; k < A.bytes / 16; k += kPBlock) dst[k] = src[k];
+        stage_lds(s_scene, A.base, A.bytes / 16, kPBlock);
     }
     if (LST) {  // the BVH node packet (the top levels of every tree)
         const persist_args& A = args_now();
-        const uint4* src = reinterpret_cast<const uint4*>(A.S.nodes);
-        uint4* dst = reinterpret_cast<uint4*>(s_scene + A.lds_nodes_off);
         constexpr uint32_t kNode16 = (uint32_t)(sizeof(node_store) / 16);
-        for (uint32_t k = threadIdx.x; k < A.lds_nodes * kNode16; k += kPBlock) dst[k] = src[k];
+        stage_lds(s_scene + A.lds_nodes_off, A.S.nodes, A.lds_nodes * kNode16, kPBlock);
     }
     if (LDS || LST) __syncthreads();
-    const uint32_t lane = threadIdx.x & 63;
     const int own = blockIdx.x % kQShards;
     path_st x;
     x.depth = 0;
@@ -839,7 +881,9 @@ void k_persist(persist_args) {
                     const persist_args& A = args_now();
                     const job_t& J = A.J;
                     ctrs_t* const C = A.C;
-                    // reserve up to NB ids, own shard first
+                    // reserve up to NB ids, own shard first: reserve_samples' loop spelt out
+                    // with rank = lane and every lane eligible (see there: a change to the
+                    // queue is made in every copy)
                     uint32_t left = NB, given = 0, q = 0;
                     bool got = false;
                     for (int a = 0; a < kQShards && left; ++a) {
@@ -970,14 +1014,7 @@ void k_persist(persist_args) {
         }
     }
     pf.flush();
-    for (int off = 32; off > 0; off >>= 1) segs += __shfl_down(segs, off, 64);
-    if (lane == 0) s_cnt[threadIdx.x >> 6] = segs;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int k = 0; k < kPWaves; ++k) t += s_cnt[k];
-        if (t) atomicAdd(&args_now().C->segments[blockIdx.x % 8].v, t);
-    }
+    count_segments<kPWaves>(segs, s_cnt, [] { return args_now().C; });
 }
 
 // Persistent form with material regrouping.  A wave pays for every shading
@@ -1037,7 +1074,96 @@ __device__ __forceinline__ uint32_t sort_base_dpp(const uint32_t (*s_kc)[4], uin
     idle_total = (uint32_t)__builtin_amdgcn_readlane((int)tot, k_idle);
     return (uint32_t)__builtin_amdgcn_ds_bpermute(key << 2, (int)base);
 }
-static_assert(kSortWaves == 4 && K_N <= kKeySlots, "sort_base_dpp: 256-thread sort blocks, at most 8 keys");
+static_assert(kSortWaves == 4 && K_N <= kKeySlots && rtwf::FK_N <= kKeySlots,
+              "sort_base_dpp: 256-thread sort blocks, at most 8 keys");
+// Step 3 of the regrouping kernels, the counting sort of the block's paths
+// by key: per key, the wave's ballot gives the lane's rank among its wave's
+// lanes of that key and, into s_kc, their count; after the barrier
+// sort_base_dpp adds the slots before them.  Returns the slot of this lane's
+// record in the sorted block.  Keys the kernel cannot produce (`used` false)
+// are skipped: their counts stay 0 (s_kc's slots start zeroed, the prefix
+// reads them).
+template <int NKEYS, class Used>
+__device__ __forceinline__ uint32_t sort_slot(uint32_t (*s_kc)[kSortWaves], uint32_t lane, uint32_t wave, int key,
+                                              int k_idle, Used used, uint32_t& idle_total) {
+    uint32_t rank_in_wave = 0;
+#pragma unroll
+    for (int k = 0; k < NKEYS; ++k) {
+        if (!used(k)) continue;
+        const unsigned long long m = __ballot(key == k);
+        if (key == k) rank_in_wave = (uint32_t)__popcll(m & lanemask_lt());
+        if (lane == 0) s_kc[k][wave] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    return rank_in_wave + sort_base_dpp(s_kc, lane, wave, key, k_idle, idle_total);
+}
+
+// The regrouping kernels' exchange (LDS, SoA): one path record per slot, in
+// the kernel's scalar T (double: k_persist_sort, float: k_fast_sort).
+// Between iterations a lane's path record sits in its own exchange slot
+// (ray, home index, sample id at [tid]); only the engine and the depth
+// are loop-carried registers.  A loop-carried ray would hold 12 VGPRs
+// through every shading branch (exec-masked branches run one after the
+// other, so a value live into any of them is live across all) -- that
+// is what pushed k_persist_sort past 96 VGPRs into scratch.
+// Path throughputs stay put: each path record (live or idle) owns one
+// home slot of thr and carries its index through the exchange, so the
+// throughput is read and written only where shading uses it and is never
+// held in registers across traversal and sort.  A lane whose path ended
+// keeps the record's slot for the camera sample it takes next.
+template <typename T>
+struct exch_types;
+template <>
+struct exch_types<double> {
+    using vec_t = d3;
+    using ray_t = ray;
+};
+template <>
+struct exch_types<float> {
+    using vec_t = rtwf::f3;
+    using ray_t = rtwf::fray;
+};
+// The arrays are static members, LDS variables of their own as the kernels'
+// other __shared__ arrays are (one set per T and TIME, allocated in every
+// kernel that uses them; the time array of a TIME false exchange is never
+// referenced and takes no LDS).  TIME false -- F_STATIC scenes -- keeps no
+// ray times: they are never read.
+template <typename T, bool TIME = true>
+struct exchange_t {
+    using vec_t = typename exch_types<T>::vec_t;
+    using ray_t = typename exch_types<T>::ray_t;
+    inline static __shared__ T o[3][kSortBlock], d[3][kSortBlock], tm[kSortBlock], t[kSortBlock];
+    inline static __shared__ int32_t prim[kSortBlock];
+    inline static __shared__ uint32_t rng[kSortBlock], depth[kSortBlock], q[kSortBlock], home[kSortBlock];
+    inline static __shared__ T thr[3][kSortBlock];  // the home slots
+    // the record's ray in slot `s`
+    __device__ __forceinline__ ray_t ray_at(uint32_t s) const {
+        return ray_t{vec_t{o[0][s], o[1][s], o[2][s]}, vec_t{d[0][s], d[1][s], d[2][s]}, TIME ? tm[s] : T(0)};
+    }
+    // (origin and direction alone: a continuation ray whose time the slot holds already)
+    __device__ __forceinline__ void put_ray_od(uint32_t s, const ray_t& r) const {
+        o[0][s] = r.o.x, o[1][s] = r.o.y, o[2][s] = r.o.z;
+        d[0][s] = r.d.x, d[1][s] = r.d.y, d[2][s] = r.d.z;
+    }
+    __device__ __forceinline__ void put_ray(uint32_t s, const ray_t& r) const {
+        put_ray_od(s, r);
+        if constexpr (TIME) tm[s] = r.t;
+    }
+    // Step 4: this lane's record to slot `dst` (an idle record's ray is
+    // garbage and stays behind).  Its home and sample id were read from the
+    // lane's own slot before the barrier that precedes these writes.
+    __device__ __forceinline__ void move_to(uint32_t dst, const ray_t& r, T hit_t, int32_t hit_prim, uint32_t rng_,
+                                            uint32_t depth_, uint32_t home_, uint32_t q_) const {
+        if (depth_ != 0) put_ray(dst, r);
+        home[dst] = home_;
+        t[dst] = hit_t;
+        prim[dst] = hit_prim;
+        rng[dst] = rng_;
+        depth[dst] = depth_;
+        q[dst] = q_;
+    }
+};
+
 template <int F, int M, bool LDS>
 __global__ __launch_bounds__(kSortBlock) __attribute__((amdgpu_waves_per_eu(RTW_PERSIST_WAVES(F, M))))
 void k_persist_sort(persist_args) {
@@ -1045,38 +1171,11 @@ void k_persist_sort(persist_args) {
     __shared__ __attribute__((aligned(16))) uint32_t s_kc[kKeySlots][kSortWaves];  // per key, lanes per wave
     if (threadIdx.x < kKeySlots * kSortWaves) (&s_kc[0][0])[threadIdx.x] = 0u;  // (before the barrier below)
     __shared__ uint32_t s_seg[kSortWaves];
-    // the exchange: one path per slot (SoA)
-    __shared__ double x_o[3][kSortBlock], x_d[3][kSortBlock], x_tm[kSortBlock], x_t[kSortBlock];
-    __shared__ int32_t x_prim[kSortBlock];
-    __shared__ uint32_t x_rng[kSortBlock], x_depth[kSortBlock], x_q[kSortBlock], x_home[kSortBlock];
-    // the record's ray in slot `s`
-    auto ray_at = [&](uint32_t s) {
-        return ray{d3{x_o[0][s], x_o[1][s], x_o[2][s]}, d3{x_d[0][s], x_d[1][s], x_d[2][s]},
-                   (F & F_STATIC) ? 0.0 : x_tm[s]};
-    };
-    auto put_ray = [&](uint32_t s, const ray& r) {
-        x_o[0][s] = r.o.x, x_o[1][s] = r.o.y, x_o[2][s] = r.o.z;
-        x_d[0][s] = r.d.x, x_d[1][s] = r.d.y, x_d[2][s] = r.d.z;
-        if constexpr (!(F & F_STATIC)) x_tm[s] = r.t;
-    };
-    // Path throughputs stay put: each path record (live or idle) owns one
-    // home slot of s_thr and carries its index through the exchange, so the
-    // throughput is read and written only where shading uses it and is never
-    // held in registers across traversal and sort.  A lane whose path ended
-    // keeps the record's slot for the camera sample it takes next.
-    __shared__ double s_thr[3][kSortBlock];
-    // Between iterations a lane's path record sits in its own exchange slot
-    // (ray, home index, sample id at [tid]); only the engine and the depth
-    // are loop-carried registers.  A loop-carried ray would hold 12 VGPRs
-    // through every shading branch (exec-masked branches run one after the
-    // other, so a value live into any of them is live across all) -- that
-    // is what pushed this kernel past 96 VGPRs into scratch.
-    x_home[threadIdx.x] = threadIdx.x;
+    const exchange_t<double, !(F & F_STATIC)> X;  // (F_STATIC: the time is never read)
+    X.home[threadIdx.x] = threadIdx.x;
     if (LDS) {
         const persist_args& A = args_now();
-        const uint4* src = reinterpret_cast<const uint4*>(A.base);
-        uint4* dst = reinterpret_cast<uint4*>(s_scene);
-        for (uint32_t k = threadIdx.x; k < A.bytes / 16; k += kSortBlock) dst[k] = src[k];
+        stage_lds(s_scene, A.base, A.bytes / 16, kSortBlock);
     }
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1092,6 +1191,8 @@ void k_persist_sort(persist_args) {
             const bool idle = x.depth == 0;
             const unsigned long long m = __ballot(idle);
             if (open && __popcll(m) >= RTW_REFILL_MIN) {
+                // reserve_samples' loop spelt out, as in k_persist (see there: a change
+                // to the queue is made in every copy)
                 const persist_args& A = args_now();
                 const job_t& J = A.J;
                 ctrs_t* const C = A.C;
@@ -1122,11 +1223,11 @@ void k_persist_sort(persist_args) {
                 if (got) {
                     const ray r = camera_sample(J, q, x.rng);
                     const uint32_t me = threadIdx.x;
-                    const uint32_t home = x_home[me];
-                    put_ray(me, r);  // (F_STATIC: the time is never read)
-                    x_q[me] = q;
+                    const uint32_t home = X.home[me];
+                    X.put_ray(me, r);
+                    X.q[me] = q;
                     x.depth = (uint32_t)J.max_depth;
-                    s_thr[0][home] = 1.0, s_thr[1][home] = 1.0, s_thr[2][home] = 1.0;
+                    X.thr[0][home] = 1.0, X.thr[1][home] = 1.0, X.thr[2][home] = 1.0;
                 }
             }
         }
@@ -1137,7 +1238,7 @@ void k_persist_sort(persist_args) {
         int key = K_IDLE;
         if (x.depth != 0) {
             const uint32_t me = threadIdx.x;
-            x.r = ray_at(me);
+            x.r = X.ray_at(me);
             const persist_args& A = args_now();
             const scene SS = LDS ? lds_scene(A.S, A.base, s_scene) : A.S;
             const hit_state h = world_closest<F>(A.S, x.r, x.rng);
@@ -1160,85 +1261,61 @@ void k_persist_sort(persist_args) {
         // 3. counting sort of the block's paths by key (the record's home and
         // sample id are read from the lane's own slot before the barrier that
         // precedes the exchange's writes)
-        const uint32_t my_home = x_home[threadIdx.x], my_q = x_q[threadIdx.x];
-        uint32_t rank_in_wave = 0;
-        // keys the scene's material set cannot produce are skipped (their
-        // counts stay 0; keep s_kc's slots zero for the prefix below)
+        const uint32_t my_home = X.home[threadIdx.x], my_q = X.q[threadIdx.x];
+        // (keys the scene's material set cannot produce are skipped)
         constexpr auto key_used = [](int k) {
             return !((k == K_METAL && !(M & SF_METAL)) || (k == K_ISO && !(M & SF_ISO)));
         };
-#pragma unroll
-        for (int k = 0; k < K_N; ++k) {
-            if (!key_used(k)) continue;
-            const unsigned long long m = __ballot(key == k);
-            if (key == k) rank_in_wave = (uint32_t)__popcll(m & lanemask_lt());
-            if (lane == 0) s_kc[k][wave] = (uint32_t)__popcll(m);
-        }
-        __syncthreads();
         uint32_t idle_total;
-        const uint32_t dst = rank_in_wave + sort_base_dpp(s_kc, lane, wave, key, K_IDLE, idle_total);
+        const uint32_t dst = sort_slot<K_N>(s_kc, lane, wave, key, K_IDLE, key_used, idle_total);
         if (idle_total == kSortBlock) break;  // block-uniform: nothing left to trace or take
         pk.mark(PS_HIT);
-        // 4. move every path to the slot of its rank (an idle record's ray
-        // is garbage and stays behind)
-        if (x.depth != 0) put_ray(dst, x.r);
-        x_home[dst] = my_home;
-        x_t[dst] = th;
-        x_prim[dst] = hp;
-        x_rng[dst] = x.rng;
-        x_depth[dst] = x.depth;
-        x_q[dst] = my_q;
+        // 4. move every path to the slot of its rank
+        X.move_to(dst, x.r, th, hp, x.rng, x.depth, my_home, my_q);
         __syncthreads();
         // (opaque, so the exchange's per-lane LDS addresses are formed here
         // from one register, not hoisted out of the loop one per array)
         uint32_t me = threadIdx.x;
         asm volatile("" : "+v"(me));
-        x.rng = x_rng[me];
-        x.depth = x_depth[me];
+        x.rng = X.rng[me];
+        x.depth = X.depth[me];
         pk.mark(PS_SAMPLE);
         // 5. shading, now mostly one branch per wave
         if (x.depth != 0) {
-            x.r = ray_at(me);
+            x.r = X.ray_at(me);
             const persist_args& A = args_now();
             const scene SS = LDS ? lds_scene(A.S, A.base, s_scene) : A.S;
             prof_t pf;
             // the outcome is applied inside the branch that produced it
             auto radiance = [&](const d3& L) {
-                double* o = A.J.L + 3 * (size_t)x_q[me];
+                double* o = A.J.L + 3 * (size_t)X.q[me];
                 store_record(o, L.x, L.y, L.z);
             };
             auto sk = make_sink(
                 [&](const d3& f, const ray& nr) {
-                    const uint32_t home = x_home[me];
-                    s_thr[0][home] *= f.x, s_thr[1][home] *= f.y, s_thr[2][home] *= f.z;
+                    const uint32_t home = X.home[me];
+                    X.thr[0][home] *= f.x, X.thr[1][home] *= f.y, X.thr[2][home] *= f.z;
                     // the continuation ray waits in the lane's own slot
-                    put_ray(me, nr);
+                    X.put_ray(me, nr);
                 },
                 [&](const d3& E) {
-                    const uint32_t home = x_home[me];
-                    radiance(d3{s_thr[0][home], s_thr[1][home], s_thr[2][home]} * E);
+                    const uint32_t home = X.home[me];
+                    radiance(d3{X.thr[0][home], X.thr[1][home], X.thr[2][home]} * E);
                 },
                 [&]() {
                     // thr * 0 (k_persist's reason: NaN / inf throughputs give NaN)
-                    const uint32_t home = x_home[me];
+                    const uint32_t home = X.home[me];
                     const double z = in_place<0>();
-                    radiance(d3{s_thr[0][home], s_thr[1][home], s_thr[2][home]} * z);
+                    radiance(d3{X.thr[0][home], X.thr[1][home], X.thr[2][home]} * z);
                 });
             const int out = shade_core<M, (F & F_STATIC) != 0, (F & F_LIGHTS) != 0, (F & F_BLACK) != 0,
-                                       (F & F_NOLIGHTS) != 0>(SS, x, x_t[me], x_prim[me], sk, pf);
+                                       (F & F_NOLIGHTS) != 0>(SS, x, X.t[me], X.prim[me], sk, pf);
             if (out != SEG_CONTINUE) x.depth = 0;
         }
         pk.mark(PS_STORE);
     }
     pk.flush();
-    for (int off = 32; off > 0; off >>= 1) segs += __shfl_down(segs, off, 64);
-    if (lane == 0) s_seg[wave] = segs;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int k = 0; k < kSortWaves; ++k) t += s_seg[k];
-        if (t) atomicAdd(&args_now().C->segments[blockIdx.x % 8].v, t);
-    }
+    count_segments<kSortWaves>(segs, s_seg, [] { return args_now().C; });
 }
 
 // ----------------------------------------------------------------------
@@ -1301,14 +1378,9 @@ void k_fast(fast_args) {
     __shared__ uint32_t s_cnt[kFW];
     if (LST) {  // the BVH node packet (the top levels of every tree)
         const fast_args& A = fast_args_now();
-        const uint4* src = reinterpret_cast<const uint4*>(A.S.nodes);
-        uint4* dst = reinterpret_cast<uint4*>(s_nodes);
-        for (uint32_t k = threadIdx.x; k < A.lds_nodes * (uint32_t)(sizeof(node_store) / 16); k += kFB)
-            dst[k] = src[k];
+        stage_lds(s_nodes, A.S.nodes, A.lds_nodes * (uint32_t)(sizeof(node_store) / 16), kFB);
         __syncthreads();
     }
-    const uint32_t lane = threadIdx.x & 63;
-    const int own = blockIdx.x % kQShards;
     fray r{f3{0, 0, 0}, f3{0, 0, 1}, 0};
     f3 thr{1, 1, 1};
     uint32_t rng = 0, depth = 0, q = 0, segs = 0;
@@ -1319,39 +1391,12 @@ void k_fast(fast_args) {
         const unsigned long long m = __ballot(idle);
         if (open && m) {
             const fast_args& A = fast_args_now();
-            const uint32_t want = (uint32_t)__popcll(m);
-            const uint32_t rank = (uint32_t)__popcll(m & lanemask_lt());
-            uint32_t left = want, given = 0, nq = 0;
-            bool got = false;
-            for (int a = 0; a < kQShards && left; ++a) {
-                const int sh = (own + a) % kQShards;
-                const unsigned long long lim = shard_limit(sh, A.J.total);
-                unsigned long long b = ~0ull;
-                if (lane == 0) {
-                    const bool dry = a > 0 && __hip_atomic_load(&A.C->qshard[sh].v, __ATOMIC_RELAXED,
-                                                                __HIP_MEMORY_SCOPE_AGENT) >= lim;
-                    if (!dry) b = atomicAdd(&A.C->qshard[sh].v, (unsigned long long)left);
-                }
-                b = __shfl(b, 0, 64);
-                if (b == ~0ull || b >= lim) continue;
-                const uint32_t ok = (uint32_t)min((unsigned long long)left, lim - b);
-                if (idle && rank >= given && rank < given + ok) {
-                    nq = (uint32_t)shard_sample(sh, b + (rank - given));
-                    got = true;
-                }
-                given += ok;
-                left -= ok;
-            }
-            if (left) open = false;
-            if (got) {
-                int i, j, sm;
-                sample_coords(A.J, nq, i, j, sm);
-                rng = path_seed(A.J.seed_mix, (uint32_t)(j * A.J.nx + i), (uint32_t)sm);
-                const float u = ((float)i + u01(rng)) * rcp((float)A.J.nx);
-                const float v = ((float)j + u01(rng)) * rcp((float)A.J.ny);
-                r = camera_ray(A.cam, u, v, rng);
+            const reservation rs = reserve_samples(A.C, A.J.total, m, idle);
+            open = rs.open;
+            if (rs.got) {
+                r = camera_sample_f32(A.J, A.cam, rs.q, rng);
                 thr = f3{1, 1, 1};
-                q = nq;
+                q = rs.q;
                 depth = (uint32_t)A.J.max_depth;
             }
         }
@@ -1386,14 +1431,7 @@ void k_fast(fast_args) {
             depth = 0;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) segs += __shfl_down(segs, off, 64);
-    if (lane == 0) s_cnt[threadIdx.x >> 6] = segs;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int k = 0; k < kFW; ++k) t += s_cnt[k];
-        if (t) atomicAdd(&fast_args_now().C->segments[blockIdx.x % 8].v, t);
-    }
+    count_segments<kFW>(segs, s_cnt, [] { return fast_args_now().C; });
 }
 
 // k_fast_sort re-points its scene with the host's offsets
@@ -1436,23 +1474,14 @@ void k_fast_sort(fast_args, const char* base, uint32_t bytes) {
     using namespace rtwf;
     constexpr bool NOISE = (F & FF_NONOISE) == 0;
     extern __shared__ __attribute__((aligned(16))) char s_scene[];
-    static_assert(FK_N <= kKeySlots, "sort_base_dpp: at most 8 keys");
     __shared__ __attribute__((aligned(16))) uint32_t s_kc[kKeySlots][kSortWaves];  // per key, lanes per wave
     if (threadIdx.x < kKeySlots * kSortWaves) (&s_kc[0][0])[threadIdx.x] = 0u;  // (before the barrier below)
     __shared__ uint32_t s_seg[kSortWaves];
-    __shared__ float x_o[3][kSortBlock], x_d[3][kSortBlock], x_tm[kSortBlock], x_t[kSortBlock];
-    __shared__ int32_t x_prim[kSortBlock];
-    __shared__ uint32_t x_rng[kSortBlock], x_depth[kSortBlock], x_q[kSortBlock], x_home[kSortBlock];
-    __shared__ float s_thr[3][kSortBlock];
-    x_home[threadIdx.x] = threadIdx.x;
-    if (LDS) {
-        const uint4* src = reinterpret_cast<const uint4*>(base);
-        uint4* dst = reinterpret_cast<uint4*>(s_scene);
-        for (uint32_t k = threadIdx.x; k < bytes / 16; k += kSortBlock) dst[k] = src[k];
-    }
+    const exchange_t<float> X;
+    X.home[threadIdx.x] = threadIdx.x;
+    if (LDS) stage_lds(s_scene, base, bytes / 16, kSortBlock);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int own = blockIdx.x % kQShards;
     uint32_t rng = 0, depth = 0, segs = 0;
     bool open = true;  // wave-uniform: the queue may still hold samples
     for (;;) {
@@ -1463,43 +1492,16 @@ void k_fast_sort(fast_args, const char* base, uint32_t bytes) {
             const unsigned long long m = __ballot(idle);
             if (open && m) {
                 const fast_args& A = fast_args_now();
-                const uint32_t rank = (uint32_t)__popcll(m & lanemask_lt());
-                uint32_t left = (uint32_t)__popcll(m), given = 0, q = 0;
-                bool got = false;
-                for (int a = 0; a < kQShards && left; ++a) {
-                    const int sh = (own + a) % kQShards;
-                    const unsigned long long lim = shard_limit(sh, A.J.total);
-                    unsigned long long b = ~0ull;
-                    if (lane == 0) {
-                        const bool dry = a > 0 && __hip_atomic_load(&A.C->qshard[sh].v, __ATOMIC_RELAXED,
-                                                                    __HIP_MEMORY_SCOPE_AGENT) >= lim;
-                        if (!dry) b = atomicAdd(&A.C->qshard[sh].v, (unsigned long long)left);
-                    }
-                    b = __shfl(b, 0, 64);
-                    if (b == ~0ull || b >= lim) continue;
-                    const uint32_t ok = (uint32_t)min((unsigned long long)left, lim - b);
-                    if (idle && rank >= given && rank < given + ok) {
-                        q = (uint32_t)shard_sample(sh, b + (rank - given));
-                        got = true;
-                    }
-                    given += ok;
-                    left -= ok;
-                }
-                if (left) open = false;
-                if (got) {
-                    int i, j, sm;
-                    sample_coords(A.J, q, i, j, sm);
-                    rng = path_seed(A.J.seed_mix, (uint32_t)(j * A.J.nx + i), (uint32_t)sm);
-                    const float u = ((float)i + u01(rng)) * rcp((float)A.J.nx);
-                    const float v = ((float)j + u01(rng)) * rcp((float)A.J.ny);
-                    const fray r = camera_ray(A.cam, u, v, rng);
-                    x_o[0][me] = r.o.x, x_o[1][me] = r.o.y, x_o[2][me] = r.o.z;
-                    x_d[0][me] = r.d.x, x_d[1][me] = r.d.y, x_d[2][me] = r.d.z;
-                    x_tm[me] = r.t;
-                    x_q[me] = q;
+                const reservation rs = reserve_samples(A.C, A.J.total, m, idle);
+                const uint32_t q = rs.q;
+                open = rs.open;
+                if (rs.got) {
+                    const fray r = camera_sample_f32(A.J, A.cam, q, rng);
+                    X.put_ray(me, r);
+                    X.q[me] = q;
                     depth = (uint32_t)A.J.max_depth;
-                    const uint32_t home = x_home[me];
-                    s_thr[0][home] = 1.0f, s_thr[1][home] = 1.0f, s_thr[2][home] = 1.0f;
+                    const uint32_t home = X.home[me];
+                    X.thr[0][home] = 1.0f, X.thr[1][home] = 1.0f, X.thr[2][home] = 1.0f;
                 }
             }
         }
@@ -1508,7 +1510,7 @@ void k_fast_sort(fast_args, const char* base, uint32_t bytes) {
         int key = FK_IDLE;
         fray r;
         if (depth != 0) {
-            r = fray{f3{x_o[0][me], x_o[1][me], x_o[2][me]}, f3{x_d[0][me], x_d[1][me], x_d[2][me]}, x_tm[me]};
+            r = X.ray_at(me);
             priv_stackf stk;
             h = world_closest<F>(fast_args_now().S, r, rng, stk);
             ++segs;
@@ -1516,60 +1518,34 @@ void k_fast_sort(fast_args, const char* base, uint32_t bytes) {
             key = hit_key(LDS ? lds_fscene_off(A.S, A.lds_off, s_scene) : A.S, h);
         }
         // 3. counting sort of the block's paths by key
-        const uint32_t my_home = x_home[me], my_q = x_q[me];
-        uint32_t rank_in_wave = 0;
-#pragma unroll
-        for (int k = 0; k < FK_N; ++k) {
-            const unsigned long long m = __ballot(key == k);
-            if (key == k) rank_in_wave = (uint32_t)__popcll(m & lanemask_lt());
-            if (lane == 0) s_kc[k][wave] = (uint32_t)__popcll(m);
-        }
-        __syncthreads();
+        const uint32_t my_home = X.home[me], my_q = X.q[me];
         uint32_t idle_total;
-        const uint32_t dst = rank_in_wave + sort_base_dpp(s_kc, lane, wave, key, FK_IDLE, idle_total);
+        const uint32_t dst = sort_slot<FK_N>(s_kc, lane, wave, key, FK_IDLE, [](int) { return true; }, idle_total);
         if (idle_total == kSortBlock) break;  // block-uniform: nothing left to trace or take
         // 4. move every path to the slot of its rank
-        if (depth != 0) {
-            x_o[0][dst] = r.o.x, x_o[1][dst] = r.o.y, x_o[2][dst] = r.o.z;
-            x_d[0][dst] = r.d.x, x_d[1][dst] = r.d.y, x_d[2][dst] = r.d.z;
-            x_tm[dst] = r.t;
-        }
-        x_home[dst] = my_home;
-        x_t[dst] = h.t;
-        x_prim[dst] = h.prim;
-        x_rng[dst] = rng;
-        x_depth[dst] = depth;
-        x_q[dst] = my_q;
+        X.move_to(dst, r, h.t, h.prim, rng, depth, my_home, my_q);
         __syncthreads();
-        rng = x_rng[me];
-        depth = x_depth[me];
+        rng = X.rng[me];
+        depth = X.depth[me];
         // 5. shading, now mostly one branch per wave
         if (depth != 0) {
-            const fray rr{f3{x_o[0][me], x_o[1][me], x_o[2][me]}, f3{x_d[0][me], x_d[1][me], x_d[2][me]}, x_tm[me]};
-            const fhit hh{x_t[me], x_prim[me], false};
+            const fray rr = X.ray_at(me);
+            const fhit hh{X.t[me], X.prim[me], false};
             const fast_args& A = fast_args_now();
             const seg_f sg = shade<NOISE>(LDS ? lds_fscene_off(A.S, A.lds_off, s_scene) : A.S, rr, hh, rng, depth);
-            const uint32_t home = x_home[me];
-            const f3 thr{s_thr[0][home], s_thr[1][home], s_thr[2][home]};
+            const uint32_t home = X.home[me];
+            const f3 thr{X.thr[0][home], X.thr[1][home], X.thr[2][home]};
             if (sg.cont) {
-                s_thr[0][home] = thr.x * sg.w.x, s_thr[1][home] = thr.y * sg.w.y, s_thr[2][home] = thr.z * sg.w.z;
-                x_o[0][me] = sg.next.o.x, x_o[1][me] = sg.next.o.y, x_o[2][me] = sg.next.o.z;
-                x_d[0][me] = sg.next.d.x, x_d[1][me] = sg.next.d.y, x_d[2][me] = sg.next.d.z;
+                X.thr[0][home] = thr.x * sg.w.x, X.thr[1][home] = thr.y * sg.w.y, X.thr[2][home] = thr.z * sg.w.z;
+                X.put_ray_od(me, sg.next);  // the continuation ray waits in the lane's own slot
                 --depth;
             } else {
-                store_record_f32(A.J.L, x_q[me], thr.x * sg.w.x, thr.y * sg.w.y, thr.z * sg.w.z);
+                store_record_f32(A.J.L, X.q[me], thr.x * sg.w.x, thr.y * sg.w.y, thr.z * sg.w.z);
                 depth = 0;
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) segs += __shfl_down(segs, off, 64);
-    if (lane == 0) s_seg[wave] = segs;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int k = 0; k < kSortWaves; ++k) t += s_seg[k];
-        if (t) atomicAdd(&fast_args_now().C->segments[blockIdx.x % 8].v, t);
-    }
+    count_segments<kSortWaves>(segs, s_seg, [] { return fast_args_now().C; });
 }
 
 // Block-wide exclusive prefix sum of one value per thread (blockDim = kBlock).
@@ -1664,13 +1640,6 @@ __global__ __launch_bounds__(kBlock) void k_regen(job_t J, paths_t P, fresh_t FR
             k -= s_got[a];
         }
     }
-}
-
-// true once every queue shard has handed out all of its samples
-inline bool queue_drained(const ctrs_t& c, uint32_t total) {
-    for (int s = 0; s < kQShards; ++s)
-        if (c.qshard[s].v < shard_limit(s, total)) return false;
-    return true;
 }
 
 // Tail-phase stream compaction of live slots (depth != 0) from A into B
@@ -2474,8 +2443,7 @@ extern "C" int rtw_finalize_canvas_device(void* handle, const double* accum, int
         return rtw_fail(RTW_ERR_INVALID, "rtw_finalize_canvas_device: bad argument");
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)nx * (size_t)ny * 3;
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 8192)), dim3(kBlock), 0,
-                       h->stream, accum, n, (double)spp, canvas);
+    hipLaunchKernelGGL(k_finalize, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, accum, n, (double)spp, canvas);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     return RTW_OK;
@@ -2754,30 +2722,23 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
         stats.samples += J.total;
     }
 
-    // accum += run
-    double* acc_dev = accum_rgb;
-    const size_t img_bytes = (size_t)R.nx * R.ny * 24;
-    if (!R.accum_on_device) {
-        if ((rc = h->accum.ensure(img_bytes))) return rc;
-        acc_dev = static_cast<double*>(h->accum.p);
-        HIPCHK(hipMemcpyAsync(acc_dev, accum_rgb, img_bytes, hipMemcpyHostToDevice, st));
-    }
-    hipLaunchKernelGGL(k_emit, dim3(std::min<uint64_t>((npix + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st, run,
-                       (uint32_t)npix, R.nx, R.row_begin, row_step, acc_dev);
-    HIPCHK(hipGetLastError());
-    if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(accum_rgb, acc_dev, img_bytes, hipMemcpyDeviceToHost, st));
-    if (accum_sq) {  // accum_sq += run2, the same way
-        double* sq_dev = accum_sq;
+    // acc += sums (the caller's accumulator: through `staging` when it is host memory)
+    auto emit = [&](double* acc, const double* sums, dev_buf& staging) -> int {
+        double* acc_dev = acc;
+        const size_t img_bytes = (size_t)R.nx * R.ny * 24;
         if (!R.accum_on_device) {
-            if ((rc = h->accum_sq.ensure(img_bytes))) return rc;
-            sq_dev = static_cast<double*>(h->accum_sq.p);
-            HIPCHK(hipMemcpyAsync(sq_dev, accum_sq, img_bytes, hipMemcpyHostToDevice, st));
+            if (int e = staging.ensure(img_bytes)) return e;
+            acc_dev = static_cast<double*>(staging.p);
+            HIPCHK(hipMemcpyAsync(acc_dev, acc, img_bytes, hipMemcpyHostToDevice, st));
         }
         hipLaunchKernelGGL(k_emit, dim3(std::min<uint64_t>((npix + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st,
-                           run2, (uint32_t)npix, R.nx, R.row_begin, row_step, sq_dev);
+                           sums, (uint32_t)npix, R.nx, R.row_begin, row_step, acc_dev);
         HIPCHK(hipGetLastError());
-        if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(accum_sq, sq_dev, img_bytes, hipMemcpyDeviceToHost, st));
-    }
+        if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(acc, acc_dev, img_bytes, hipMemcpyDeviceToHost, st));
+        return RTW_OK;
+    };
+    if ((rc = emit(accum_rgb, run, h->accum))) return rc;
+    if (accum_sq && (rc = emit(accum_sq, run2, h->accum_sq))) return rc;
     HIPCHK(hipMemcpyAsync(&h->host_ctrs[63], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(ev_end, st));
     HIPCHK(hipStreamSynchronize(st));
