@@ -45,10 +45,11 @@ PUBLIC_HEADERS = [ROOT / "include" / "rtw_gpu.h", ROOT / "include" / "rtw_noise.
 HEADERS = sorted(list(CSRC.rglob("*.h")) + PUBLIC_HEADERS)
 # what the device sources include: the build id and the kernels' rebuilds
 # follow these only (the host scene API headers under csrc/host/rtw/ do not
-# reach the kernels; host/scene_layout.h does: upload_scene and the handle
-# hold its result types by value)
+# reach the kernels; host/scene_layout.h and host/render_plan.h do:
+# upload_scene, the handle and render_accumulate hold their result types by
+# value)
 DEVICE_HEADERS = sorted([*CSRC.glob("rtw_*.h"), CSRC / "host" / "rtw_host_util.h", CSRC / "host" / "scene_layout.h",
-                         *PUBLIC_HEADERS])
+                         CSRC / "host" / "render_plan.h", *PUBLIC_HEADERS])
 # RCCL for rtw_render_multi (multi.cpp); the same librccl.so.1 torch loads
 LIBS = ["-L/opt/rocm/lib", "-lrccl"]
 

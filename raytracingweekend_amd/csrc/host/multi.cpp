@@ -21,6 +21,7 @@
 #include <string>
 #include <thread>
 #include <vector>
+#include "render_plan.h"
 #include "rtw_host_util.h"
 
 namespace {
@@ -107,10 +108,8 @@ extern "C" int rtw_render_multi(int ngpus, void* const* handles, const rtw_camer
     if (ngpus <= 0 || !handles || !camera || !params || !accum_root)
         return rtw_fail(RTW_ERR_INVALID, "rtw_render_multi: bad argument");
     const rtw_render_params& R = *params;
-    if (R.nx <= 0 || R.ny <= 0 || R.spp <= 0 || R.spp_begin < 0 || R.spp_begin > R.spp || R.spp_count < 0)
-        return rtw_fail(RTW_ERR_INVALID, "rtw_render_multi: bad image / sample parameters");
-    const int count = R.spp_count ? R.spp_count : R.spp - R.spp_begin;
-    if (R.spp_begin + (long long)count > R.spp) return rtw_fail(RTW_ERR_INVALID, "rtw_render_multi: sample range exceeds spp");
+    int count = 0;
+    if (int rc = rtw_check_sample_range(R, "rtw_render_multi", "rtw_render_multi: ", &count)) return rc;
     std::vector<int> devs(ngpus);
     for (int g = 0; g < ngpus; ++g) {
         devs[g] = rtw_handle_device(handles[g]);

@@ -42,6 +42,7 @@
 #include "rtw_device.h"
 #include "rtw_fast.h"
 #include "rtw_queue.h"
+#include "host/render_plan.h"
 #include "host/rtw_host_util.h"
 #include "host/scene_layout.h"
 
@@ -1844,16 +1845,13 @@ __global__ __launch_bounds__(kBlock) void k_noise_pixels(const double* __restric
             return rtw_fail(RTW_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));      \
     } while (0)
 
-uint64_t host_splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 struct dev_buf {
     void* p = nullptr;
     size_t bytes = 0;
+    dev_buf() = default;
+    dev_buf(const dev_buf&) = delete;
+    dev_buf& operator=(const dev_buf&) = delete;
+    ~dev_buf() { release(); }  // (rtw_scene_free: on the handle's device, its stream synchronised)
     int ensure(size_t n) {
         if (n <= bytes) return RTW_OK;
         if (p) hipFree(p);
@@ -1898,37 +1896,6 @@ struct handle_t {
     int cus = 256;
     std::vector<hipEvent_t> events;
 };
-
-paths_t carve_paths(void* base, uint32_t cap) {
-    char* p = static_cast<char*>(base);
-    paths_t P;
-    double** d[] = {&P.ox, &P.oy, &P.oz, &P.dx, &P.dy, &P.dz, &P.tm, &P.tr, &P.tg, &P.tb};
-    for (double** x : d) {
-        *x = reinterpret_cast<double*>(p);
-        p += (size_t)cap * 8;
-    }
-    uint32_t** u[] = {&P.rng, &P.depth, &P.qid};
-    for (uint32_t** x : u) {
-        *x = reinterpret_cast<uint32_t*>(p);
-        p += (size_t)cap * 4;
-    }
-    return P;
-}
-size_t paths_bytes(uint32_t cap) { return (size_t)cap * (10 * 8 + 3 * 4); }
-
-fresh_t carve_fresh(void* base, uint32_t cap) {
-    char* p = static_cast<char*>(base);
-    fresh_t F;
-    double** d[] = {&F.ox, &F.oy, &F.oz, &F.dx, &F.dy, &F.dz, &F.tm};
-    for (double** x : d) {
-        *x = reinterpret_cast<double*>(p);
-        p += (size_t)cap * 8;
-    }
-    F.rng = reinterpret_cast<uint32_t*>(p);
-    F.qid = F.rng + cap;
-    return F;
-}
-size_t fresh_bytes(uint32_t cap) { return (size_t)cap * (7 * 8 + 2 * 4); }
 
 // The scene on the card: rtw_layout_scene's two blobs (host/scene_layout.cpp)
 // copied as they are, and the kernels' scene structs pointed into them.
@@ -2094,6 +2061,16 @@ template <size_t... I>
 std::array<const void*, sizeof...(I)> fast_sort_rows(std::index_sequence<I...>) {
     return {reinterpret_cast<const void*>(&k_fast_sort<kFastSortList[I].f, kFastSortList[I].l>)...};
 }
+template <size_t... I>
+std::array<const void*, sizeof...(I)> shade_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_shade<kShadeList[I].m, kShadeList[I].l>)...};
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> intersect_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_intersect<kIntersectList[I].f>)...};
+}
+const auto kShadeRows = shade_rows(std::make_index_sequence<kShadeList.size()>{});
+const auto kIntersectRows = intersect_rows(std::make_index_sequence<kIntersectList.size()>{});
 const auto kPersistRows = persist_rows(std::make_index_sequence<kPersistList.size()>{});
 const auto kSegmentRows = segment_rows(std::make_index_sequence<kSegmentList.size()>{});
 const auto kFastRows = fast_rows(std::make_index_sequence<kFastList.size()>{});
@@ -2135,7 +2112,8 @@ bool fast_image_ok(const handle_t* h) {
 // launch tables and its LDS layout.  Launches nothing (occupancy queries only).
 struct plan_t {
     kernel_choice c;
-    const void* fn = nullptr;  // the kernel (the split pair: none, launch_intersect / launch_shade)
+    const void* fn = nullptr;        // the kernel (the split pair: k_intersect)
+    const void* fn_shade = nullptr;  // the split pair's k_shade
     size_t shm = 0;            // LDS bytes of the scene's shading data (0: read through the caches)
     uint32_t packet = 0;       // BVH nodes staged in LDS (persist_lst, fast with LDS stacks)
 };
@@ -2143,9 +2121,17 @@ int plan_render(const handle_t* h, bool pin, bool fast, plan_t* out) {
     select_in s = scene_facts(h, pin);
     s.env = read_env();
     plan_t p{fast ? select_fp32(s) : select_fp64(s)};
-    const inst& id = p.c.id;
-    p.shm = !id.l ? 0 : p.c.form == kform::fast_sort ? h->facts.f32_bytes : p.c.form == kform::fast ? 0 : h->facts.shade_bytes;
     const kform form = p.c.form;
+    if (form == kform::split) {  // (its rows cover every choice: split_resolve)
+        const split_rows r = split_resolve(p.c.id);
+        p.fn = kIntersectRows[index_of(kIntersectList, r.intersect)];
+        p.fn_shade = kShadeRows[index_of(kShadeList, r.shade)];
+        p.shm = r.shade.l ? h->facts.shade_bytes : 0;
+        *out = p;
+        return RTW_OK;
+    }
+    const inst& id = p.c.id;
+    p.shm = !id.l ? 0 : form == kform::fast_sort ? h->facts.f32_bytes : form == kform::fast ? 0 : h->facts.shade_bytes;
     const bool fp64 = form == kform::persist_sort || form == kform::persist || form == kform::persist_lst;
     const int at = fp64 ? index_of(kPersistList, id) : form == kform::segment ? index_of(kSegmentList, id)
                  : form == kform::fast ? index_of(kFastList, id)
@@ -2212,50 +2198,14 @@ void launch_persistent(const plan_t& p, const handle_t* h, hipStream_t st, const
     }
 }
 
+// The split pair's launches, from the plan's rows (rtw_select.h split_resolve).
 void launch_shade(const plan_t& p, int grid, hipStream_t st, const scene& S, const job_t& J, const paths_t& A,
                   const fresh_t& F, const double* ht, const int32_t* hid, ctrs_t* C, const char* base, uint32_t bytes) {
-    switch (p.c.id.m * 2 + (p.c.id.l ? 1 : 0)) {
-#define RTW_CASE(M, LDS)                                                                                   \
-    case M * 2 + (LDS ? 1 : 0):                                                                            \
-        hipLaunchKernelGGL((k_shade<M, LDS>), dim3(grid), dim3(kBlock), p.shm, st, S, J, A, F, ht, hid, C, base, bytes); \
-        break;
-#ifndef RTW_SUBSET
-        RTW_CASE(SF_DIEL, true)
-        RTW_CASE(SF_DIEL, false)
-        RTW_CASE(SF_METAL | SF_DIEL, true)
-        RTW_CASE(SF_METAL | SF_DIEL, false)
-        RTW_CASE(SF_NOISE, true)
-        RTW_CASE(SF_NOISE, false)
-        RTW_CASE(SF_ALL, true)
-        RTW_CASE(SF_IMG_ALL, false)  // (no LDS form for image scenes: select_fp64)
-#endif
-#undef RTW_CASE
-    default:
-        hipLaunchKernelGGL((k_shade<SF_ALL, false>), dim3(grid), dim3(kBlock), 0, st, S, J, A, F, ht, hid, C, base, bytes);
-    }
+    launch(p.fn_shade, grid, kBlock, p.shm, st, S, J, A, F, ht, hid, C, base, bytes);
 }
-
-// one traversal kernel per scene-feature combination (a world BVH never
-// coexists with media: validate_desc)
 void launch_intersect(const plan_t& p, int grid, hipStream_t st, const scene& S, const paths_t& A, const fresh_t& FR,
                       double* ht, int32_t* hid, ctrs_t* C) {
-    switch (p.c.id.f) {
-#define RTW_CASE(F)                                                                               \
-    case F:                                                                                       \
-        hipLaunchKernelGGL(k_intersect<F>, dim3(grid), dim3(kBlock), 0, st, S, A, FR, ht, hid, C); \
-        break;
-#ifndef RTW_SUBSET
-        RTW_CASE(0)
-        RTW_CASE(F_MEDIA)
-        RTW_CASE(F_WBVH)
-        RTW_CASE(F_GBVH)
-        RTW_CASE(F_MEDIA | F_GBVH)
-        RTW_CASE(F_WBVH | F_GBVH)
-#endif
-#undef RTW_CASE
-    default:
-        hipLaunchKernelGGL(k_intersect<F_MEDIA | F_GBVH>, dim3(grid), dim3(kBlock), 0, st, S, A, FR, ht, hid, C);
-    }
+    launch(p.fn, grid, kBlock, 0, st, S, A, FR, ht, hid, C);
 }
 
 hipEvent_t event_at(handle_t* h, size_t k) {
@@ -2415,25 +2365,10 @@ extern "C" void rtw_scene_free(void* handle) {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    h->scene_mem.release();
-    h->scene32.release();
-    h->pool[0].release();
-    h->pool[1].release();
-    h->fresh.release();
-    h->hits.release();
-    h->radiance.release();
-    h->run.release();
-    h->flog.release();
-    h->accum.release();
-    h->run2.release();
-    h->accum_sq.release();
-    h->noise.release();
-    h->ctrs.release();
-    h->camera.release();
     if (h->host_ctrs) hipHostFree(h->host_ctrs);
     for (hipEvent_t e : h->events) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;  // frees its buffers (dev_buf)
 }
 
 extern "C" int rtw_finalize_canvas_device(void* handle, const double* accum, int nx, int ny, int spp,
@@ -2449,7 +2384,39 @@ extern "C" int rtw_finalize_canvas_device(void* handle, const double* accum, int
     return RTW_OK;
 }
 
+namespace {
+
 using ev_list = std::vector<std::pair<size_t, size_t>>;  // event slots around timed launches
+
+// A call's events: slots of the handle's event list, handed out in order.
+// collect_kernel_times: 1 = events around each traversal launch (the
+// roofline kernel), 2 = also around each shade launch.  Every event pair
+// costs a few us of queue gap per iteration, so the default is neither.
+struct call_events {
+    handle_t* h;
+    size_t ev = 0;
+    ev_list isect_ev, shade_ev;
+    ev_list *time_isect = nullptr, *time_shade = nullptr;
+    call_events(handle_t* h_, int collect) : h(h_) {
+        if (collect != 0) time_isect = &isect_ev;
+        if (collect >= 2) time_shade = &shade_ev;
+    }
+    // launch(), between two events whose slots go to *list (null: untimed)
+    template <class L>
+    int timed(ev_list* list, L&& launch) {
+        if (!list) {
+            launch();
+            return RTW_OK;
+        }
+        const size_t e0 = ev++, e1 = ev++;
+        if (!event_at(h, e1)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
+        HIPCHK(hipEventRecord(h->events[e0], h->stream));
+        launch();
+        HIPCHK(hipEventRecord(h->events[e1], h->stream));
+        list->push_back({e0, e1});
+        return RTW_OK;
+    }
+};
 
 // The wavefront form's path pool and hit records.
 struct wave_pool {
@@ -2463,37 +2430,32 @@ struct wave_pool {
 // One pass of the wavefront form: fill the pool, then per iteration the plan's
 // fused k_segment or the k_intersect / k_shade pair and a refill (k_regen)
 // or, once the sample queue is drained, a compaction; ends when a status
-// snapshot shows the pool empty.  timed: render_accumulate's event helper.
-template <class T>
-int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, wave_pool& W, int max_depth, size_t& ev, T& timed,
-                   ev_list* time_isect, ev_list* time_shade, rtw_stats& stats) {
+// snapshot shows the pool empty.
+int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, const call_pass& pass, wave_pool& W, call_events& E,
+                   rtw_stats& stats) {
     hipStream_t st = h->stream;
     ctrs_t* C = static_cast<ctrs_t*>(h->ctrs.p);
     const int grid = h->grid;
     const int regen_grid = (int)((W.size + kRegenSlots - 1) / kRegenSlots);
     const int check_every = 4;
-    const uint32_t n0 = std::min<uint32_t>(W.size, J.total);
+    const uint32_t n0 = pass.fill;
     int rc;
     hipLaunchKernelGGL(k_fill, dim3((n0 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, W.A, C, n0);
     hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
     HIPCHK(hipGetLastError());
     bool tail = false;
     std::vector<size_t> checks;  // event slots of status copies, with their copy index
-    // every iteration retires >= 1 live segment; a pass needs at most
-    // total * max_depth / pool + max_depth iterations plus the lag of the
-    // status snapshots -- far beyond that the pool is not draining: fail
-    const uint64_t cap = (uint64_t)J.total * (uint64_t)max_depth / n0 + 4ull * max_depth + 64;
     for (uint64_t it = 0;; ++it) {
-        if (it > cap) return rtw_fail(RTW_ERR_HIP, "wavefront did not drain (internal error)");
+        if (it > pass.iter_cap) return rtw_fail(RTW_ERR_HIP, "wavefront did not drain (internal error)");
         if (plan.c.form == kform::segment) {
-            rc = timed(time_isect, [&] {
+            rc = E.timed(E.time_isect, [&] {
                 launch(plan.fn, grid, kBlock, plan.shm, st, h->S, J, W.A, W.FR, C, h->scene_base, h->facts.shade_bytes);
             });
             if (rc) return rc;
         } else {
-            rc = timed(time_isect, [&] { launch_intersect(plan, grid, st, h->S, W.A, W.FR, W.ht, W.hid, C); });
+            rc = E.timed(E.time_isect, [&] { launch_intersect(plan, grid, st, h->S, W.A, W.FR, W.ht, W.hid, C); });
             if (rc) return rc;
-            rc = timed(time_shade, [&] {
+            rc = E.timed(E.time_shade, [&] {
                 launch_shade(plan, grid, st, h->S, J, W.A, W.FR, W.ht, W.hid, C, h->scene_base, h->facts.shade_bytes);
             });
             if (rc) return rc;
@@ -2513,7 +2475,7 @@ int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, wave_pool& W
             // keeps `check_every` iterations of queued work
             const size_t slot = checks.size() % 64;
             HIPCHK(hipMemcpyAsync(&h->host_ctrs[slot], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
-            const size_t e = ev++;
+            const size_t e = E.ev++;
             if (!event_at(h, e)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
             HIPCHK(hipEventRecord(h->events[e], st));
             checks.push_back(e);
@@ -2527,234 +2489,98 @@ int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, wave_pool& W
     return RTW_OK;
 }
 
-// The render of rtw_render_accumulate and, with accum_sq set, of
-// rtw_render_accumulate_moments (rtw_noise.h): the same launches, allocations
-// and copies, except that k_reduce_moments takes k_reduce's place and a
-// second k_emit adds the sums of squares.  With accum_sq null nothing here
-// differs from the plain render.
-static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const rtw_render_params* prm,
-                             double* accum_rgb, double* accum_sq, rtw_stats* out_stats) {
-    const rtw_render_params& R = *prm;
-    if (R.nx <= 0 || R.ny <= 0 || R.spp <= 0 || R.spp_begin < 0 || R.spp_begin > R.spp || R.spp_count < 0)
-        return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate: bad image / sample parameters");
-    const int spp_count = R.spp_count ? R.spp_count : R.spp - R.spp_begin;
-    if (R.spp_begin + (long long)spp_count > R.spp) return rtw_fail(RTW_ERR_INVALID, "sample range exceeds spp");
-    if (R.precision != RTW_PRECISION_FP64 && R.precision != RTW_PRECISION_FP32)
-        return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate: unknown precision");
-    const int row_step = R.row_step > 0 ? R.row_step : 1;
-    if (R.row_begin < 0 || R.row_begin >= R.ny) return rtw_fail(RTW_ERR_INVALID, "row_begin out of range");
-    const int n_rows = (R.ny - R.row_begin + row_step - 1) / row_step;
-    const uint64_t npix = (uint64_t)n_rows * (uint64_t)R.nx;
-    if ((uint64_t)R.nx * R.ny >= (1ull << 32) || npix >= (1ull << 31))
-        return rtw_fail(RTW_ERR_INVALID, "image too large for 32-bit pixel ids");
-    if (h->facts.bvh_motion && (std::min(camera->time0, camera->time1) < h->facts.shutter0 ||
-                          std::max(camera->time0, camera->time1) > h->facts.shutter1))
-        return rtw_fail(RTW_ERR_INVALID,
-                        "rtw_render_accumulate: camera shutter outside the one the scene's BVH was built for "
-                        "(moving spheres); flatten the scene with this camera");
-    if (accum_sq && rtw_ranges_overlap(accum_rgb, accum_sq, (size_t)R.nx * R.ny * 24))
-        return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_moments: accum_rgb and accum_sq_rgb overlap");
-    HIPCHK(hipSetDevice(h->device));
-    if (R.accum_on_device) {
-        if (int rc = rtw_check_device_ptr(accum_rgb, h->device, "rtw_render_accumulate")) return rc;
-        if (accum_sq)
-            if (int rc = rtw_check_device_ptr(accum_sq, h->device, "rtw_render_accumulate_moments")) return rc;
-    }
-    hipStream_t st = h->stream;
-
-    rtw_stats stats;
-    std::memset(&stats, 0, sizeof stats);
-    if (spp_count == 0 || R.max_depth <= 0) {
-        // color() with depth <= 0 returns 0 (RayTracingWeekend.cpp:47-48):
-        // every sample adds zero radiance, the accumulator is unchanged.
-        stats.samples = (uint64_t)spp_count * npix;
-        if (out_stats) *out_stats = stats;
-        return RTW_OK;
-    }
-
-    // execution form: persistent (paths in registers, one launch per pass)
-    // unless RTW_MODE=wavefront or no persistent instantiation covers the
-    // scene (rtw_select.h; planning launches nothing); the strict build
-    // refuses the other forms here, before any allocation or launch
-    // fp32 fast mode: its own persistent kernel (rtw_fast.h), same passes,
-    // radiance records and ordered per-pixel reduction
-    const bool fast = R.precision == RTW_PRECISION_FP32;
-    const bool pin = camera_is_pinhole(*camera);
-    if (fast && !fast_image_ok(h))
-        return rtw_fail(RTW_ERR_UNSUPPORTED, "precision fp32 with image textures covers list and world-BVH scenes only "
-                                             "(this scene has media or group BVHs): render it in fp64");
-    plan_t plan;
-    if (int rc = plan_render(h, pin, fast, &plan)) return rc;
-    const bool persistent = plan.c.persistent();
-    if (RTW_STRICT_RADIANCE && !persistent)
-        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders with the persistent kernel only "
-                                             "(RTW_MODE=wavefront or a scene without a persistent instantiation)");
-
-    // pool and pass sizing
-    uint32_t pool = R.wavefront_paths > 0 ? (uint32_t)R.wavefront_paths : (1u << 21);
-    const size_t budget = pass_budget_samples();
-    uint64_t pass_spp = std::max<uint64_t>(1, std::min<uint64_t>(spp_count, budget / npix));
-    pass_spp = std::min<uint64_t>(pass_spp, ((1ull << 32) - 1) / npix);
-    const uint64_t pass_samples = pass_spp * npix;
-    pool = (uint32_t)std::min<uint64_t>(pool, pass_samples);
-    pool = std::max<uint32_t>(pool, 1);
-
+// Every buffer of a planned call (render_plan.h call_bytes).
+int ensure_buffers(handle_t* h, const call_bytes& b, bool moments) {
     int rc;
-    if ((rc = h->pool[0].ensure(paths_bytes(pool)))) return rc;
-    if ((rc = h->pool[1].ensure(paths_bytes(pool)))) return rc;
-    if ((rc = h->fresh.ensure(fresh_bytes(pool)))) return rc;
-    if ((rc = h->hits.ensure((size_t)pool * 12))) return rc;
-    if ((rc = h->radiance.ensure(pass_samples * 24))) return rc;
-    if ((rc = h->run.ensure(npix * 24))) return rc;
-    if (accum_sq && (rc = h->run2.ensure(npix * 24))) return rc;
-    wave_pool W{carve_paths(h->pool[0].p, pool), carve_paths(h->pool[1].p, pool), carve_fresh(h->fresh.p, pool),
-                static_cast<double*>(h->hits.p),
-                reinterpret_cast<int32_t*>(static_cast<char*>(h->hits.p) + (size_t)pool * 8), pool};
-    ctrs_t* C = static_cast<ctrs_t*>(h->ctrs.p);
-    double* run = static_cast<double*>(h->run.p);
-    double* run2 = accum_sq ? static_cast<double*>(h->run2.p) : nullptr;
-    HIPCHK(hipMemsetAsync(run, 0, npix * 24, st));
-    if (run2) HIPCHK(hipMemsetAsync(run2, 0, npix * 24, st));
-    HIPCHK(hipMemsetAsync(C, 0, sizeof(ctrs_t), st));
-    // the ordered per-pixel reduction of one pass's records (k_reduce, or with
-    // accum_sq k_reduce_moments: both sums from one read of each record)
-    auto launch_reduce = [&](bool f32, const double* L, uint32_t S_pass) {
-        const dim3 g(reduce_grid(npix)), b(kBlock);
-        const float* Lf = reinterpret_cast<const float*>(L);
-        if (run2) {
-            if (f32) hipLaunchKernelGGL(k_reduce_moments<float>, g, b, 0, st, Lf, (uint32_t)npix, S_pass, run, run2);
-            else hipLaunchKernelGGL(k_reduce_moments<double>, g, b, 0, st, L, (uint32_t)npix, S_pass, run, run2);
-        } else {
-            if (f32) hipLaunchKernelGGL(k_reduce<float>, g, b, 0, st, Lf, (uint32_t)npix, S_pass, run);
-            else hipLaunchKernelGGL(k_reduce<double>, g, b, 0, st, L, (uint32_t)npix, S_pass, run);
-        }
-    };
+    if ((rc = h->pool[0].ensure(b.pool))) return rc;
+    if ((rc = h->pool[1].ensure(b.pool))) return rc;
+    if ((rc = h->fresh.ensure(b.fresh))) return rc;
+    if ((rc = h->hits.ensure(b.hits))) return rc;
+    if ((rc = h->radiance.ensure(b.radiance))) return rc;
+    if ((rc = h->run.ensure(b.run))) return rc;
+    if ((rc = h->run2.ensure(b.run2))) return rc;
+    if ((rc = h->camera.ensure(b.camera))) return rc;
+    if ((rc = h->flog.ensure(b.flog))) return rc;
+    if ((rc = h->accum.ensure(b.staging))) return rc;
+    if (moments && (rc = h->accum_sq.ensure(b.staging))) return rc;
+    return RTW_OK;
+}
 
+// The job of a planned call on this handle's buffers, without the pass's
+// fields (set_pass).
+job_t make_job(const handle_t* h, const call_plan& P, const rtw_render_params& R) {
     job_t J;
-    h->cam_host = *camera;
-    // camera_sample<false>'s pinhole test reads lens_radius and the origin; a
-    // lens-less camera whose u or v is not finite gets lens_radius NaN in the
-    // device copy: rd = NaN * p, so its offset is NaN as the reference's
-    // u * rd.x + v * rd.y is (the same all-NaN rays, the same draws), and the
-    // shortcut does not apply
-    {
-        bool uv = true;
-        for (int k = 0; k < 3; ++k) uv = uv && std::isfinite(camera->u[k]) && std::isfinite(camera->v[k]);
-        if (!uv && h->cam_host.lens_radius == 0.0) h->cam_host.lens_radius = __builtin_nan("");
-    }
-    if ((rc = h->camera.ensure(sizeof(rtw_camera_desc) + 2 * sizeof(double)))) return rc;
-    HIPCHK(hipMemcpyAsync(h->camera.p, &h->cam_host, sizeof(rtw_camera_desc), hipMemcpyHostToDevice, st));
     J.cam = static_cast<const rtw_camera_desc*>(h->camera.p);
-    hipLaunchKernelGGL(k_recips, dim3(1), dim3(64), 0, st,
-                       reinterpret_cast<double*>(static_cast<char*>(h->camera.p) + sizeof(rtw_camera_desc)), R.nx, R.ny);
-    HIPCHK(hipGetLastError());
-    J.seed_mix = host_splitmix64(R.seed);
-    J.cam_pin = pin ? 1u : 0u;
-    J.npix = (uint32_t)npix;
-    J.nx = R.nx, J.ny = R.ny, J.row_begin = R.row_begin, J.row_step = row_step;
-    J.div_npix = rtwd::udiv_magic(J.npix);
-    J.div_nx = rtwd::udiv_magic((uint32_t)R.nx);
+    J.seed_mix = P.seed_mix;
+    J.cam_pin = P.cam_pin;
+    J.npix = (uint32_t)P.npix;
+    J.nx = R.nx, J.ny = R.ny, J.row_begin = R.row_begin, J.row_step = P.row_step;
+    J.div_npix = P.div_npix;
+    J.div_nx = P.div_nx;
     J.max_depth = R.max_depth;
     J.L = static_cast<double*>(h->radiance.p);
 #if RTW_STRICT_RADIANCE
-    // a factor log per thread of the largest resident grid (2 048 threads per
-    // CU), one 32-B entry per bounce
-    J.flog_threads = (uint32_t)h->cus * 2048u;
-    if ((rc = h->flog.ensure((size_t)J.flog_threads * (size_t)R.max_depth * 32))) return rc;
+    J.flog_threads = P.flog_threads;
     J.flog = static_cast<double*>(h->flog.p);
 #endif
+    return J;
+}
+void set_pass(job_t& J, const call_pass& p) {
+    J.total = p.total;
+    J.spp_pass = p.spp_pass;
+    J.div_spp = p.div_spp;
+    J.s_begin = p.s_begin;
+}
 
-    size_t ev = 0;
-    ev_list isect_ev, shade_ev;
-    hipEvent_t ev_begin = event_at(h, ev++), ev_end = event_at(h, ev++);
-    if (!ev_begin || !ev_end) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
-    HIPCHK(hipEventRecord(ev_begin, st));
-    // collect_kernel_times: 1 = events around each traversal launch (the
-    // roofline kernel), 2 = also around each shade launch.  Every event pair
-    // costs a few us of queue gap per iteration, so the default is neither.
-    ev_list* const time_isect = R.collect_kernel_times != 0 ? &isect_ev : nullptr;
-    ev_list* const time_shade = R.collect_kernel_times >= 2 ? &shade_ev : nullptr;
-    // launch(), between two events whose slots go to *list (null: untimed)
-    auto timed = [&](ev_list* list, auto&& launch) -> int {
-        if (!list) {
-            launch();
-            return RTW_OK;
-        }
-        const size_t e0 = ev++, e1 = ev++;
-        if (!event_at(h, e1)) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
-        HIPCHK(hipEventRecord(h->events[e0], st));
-        launch();
-        HIPCHK(hipEventRecord(h->events[e1], st));
-        list->push_back({e0, e1});
-        return RTW_OK;
-    };
+// The fp32 kernels' arguments but the job (a fast render; else zeros).
+fast_args make_fast_args(const handle_t* h, const call_plan& P) {
     fast_args FA{};
-    if (fast) {
-        FA.S = h->F32;
-        FA.C = C;
-        const rtw_camera_desc& c = *camera;
-        for (int k = 0; k < 3; ++k) {
-            FA.cam.origin[k] = (float)c.origin[k], FA.cam.lower_left[k] = (float)c.lower_left[k];
-            FA.cam.horizontal[k] = (float)c.horizontal[k], FA.cam.vertical[k] = (float)c.vertical[k];
-            FA.cam.u[k] = (float)c.u[k], FA.cam.v[k] = (float)c.v[k];
-        }
-        FA.cam.time0 = (float)c.time0, FA.cam.dtime = (float)(c.time1 - c.time0);
-        FA.cam.lens_radius = (float)c.lens_radius;
+    if (!P.fast) return FA;
+    FA.S = h->F32;
+    FA.C = static_cast<ctrs_t*>(h->ctrs.p);
+    const call_cam32& c = P.cam32;
+    for (int k = 0; k < 3; ++k) {
+        FA.cam.origin[k] = c.origin[k], FA.cam.lower_left[k] = c.lower_left[k];
+        FA.cam.horizontal[k] = c.horizontal[k], FA.cam.vertical[k] = c.vertical[k];
+        FA.cam.u[k] = c.u[k], FA.cam.v[k] = c.v[k];
     }
-    for (uint64_t done = 0; done < (uint64_t)spp_count; done += pass_spp) {
-        const uint32_t S_pass = (uint32_t)std::min<uint64_t>(pass_spp, spp_count - done);
-        J.total = (uint32_t)(S_pass * npix);
-        J.spp_pass = S_pass;
-        J.div_spp = rtwd::udiv_magic(S_pass);
-        J.s_begin = R.spp_begin + (int)done;
-        if (persistent) {
-            hipLaunchKernelGGL(k_fill, dim3(1), dim3(kBlock), 0, st, W.A, C, 0u);  // reset the queue
-            FA.J = J;
-            if ((rc = timed(time_isect, [&] { launch_persistent(plan, h, st, J, C, FA); }))) return rc;
-            HIPCHK(hipGetLastError());
-            stats.launches_intersect++;
-            stats.iterations++;
-        } else if ((rc = wavefront_pass(h, plan, J, W, R.max_depth, ev, timed, time_isect, time_shade, stats))) {
-            return rc;
-        }
-        launch_reduce(fast, J.L, S_pass);  // (the wavefront form is fp64 only)
-        HIPCHK(hipGetLastError());
-        stats.samples += J.total;
-    }
+    FA.cam.time0 = c.time0, FA.cam.dtime = c.dtime, FA.cam.lens_radius = c.lens_radius;
+    return FA;
+}
 
-    // acc += sums (the caller's accumulator: through `staging` when it is host memory)
-    auto emit = [&](double* acc, const double* sums, dev_buf& staging) -> int {
-        double* acc_dev = acc;
-        const size_t img_bytes = (size_t)R.nx * R.ny * 24;
-        if (!R.accum_on_device) {
-            if (int e = staging.ensure(img_bytes)) return e;
-            acc_dev = static_cast<double*>(staging.p);
-            HIPCHK(hipMemcpyAsync(acc_dev, acc, img_bytes, hipMemcpyHostToDevice, st));
-        }
-        hipLaunchKernelGGL(k_emit, dim3(std::min<uint64_t>((npix + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st,
-                           sums, (uint32_t)npix, R.nx, R.row_begin, row_step, acc_dev);
-        HIPCHK(hipGetLastError());
-        if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(acc, acc_dev, img_bytes, hipMemcpyDeviceToHost, st));
-        return RTW_OK;
-    };
-    if ((rc = emit(accum_rgb, run, h->accum))) return rc;
-    if (accum_sq && (rc = emit(accum_sq, run2, h->accum_sq))) return rc;
-    HIPCHK(hipMemcpyAsync(&h->host_ctrs[63], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(ev_end, st));
-    HIPCHK(hipStreamSynchronize(st));
+// The ordered per-pixel reduction of one pass's records into run (k_reduce),
+// or with run2 into both sums from one read of each record (k_reduce_moments).
+void launch_reduce(hipStream_t st, bool f32, const double* L, uint64_t npix, uint32_t S_pass, double* run, double* run2) {
+    const dim3 g(reduce_grid(npix)), b(kBlock);
+    const float* Lf = reinterpret_cast<const float*>(L);
+    if (run2) {
+        if (f32) hipLaunchKernelGGL(k_reduce_moments<float>, g, b, 0, st, Lf, (uint32_t)npix, S_pass, run, run2);
+        else hipLaunchKernelGGL(k_reduce_moments<double>, g, b, 0, st, L, (uint32_t)npix, S_pass, run, run2);
+    } else {
+        if (f32) hipLaunchKernelGGL(k_reduce<float>, g, b, 0, st, Lf, (uint32_t)npix, S_pass, run);
+        else hipLaunchKernelGGL(k_reduce<double>, g, b, 0, st, L, (uint32_t)npix, S_pass, run);
+    }
+}
 
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end));
-    stats.ms_total = ms;
-    for (int k = 0; k < 8; ++k) stats.segments += h->host_ctrs[63].segments[k].v;
-    for (auto& p : isect_ev) {
-        HIPCHK(hipEventElapsedTime(&ms, h->events[p.first], h->events[p.second]));
-        stats.ms_intersect += ms;
+// acc += sums (the caller's accumulator: through `staging` when it is host memory)
+int emit(hipStream_t st, const call_plan& P, const rtw_render_params& R, double* acc, const double* sums,
+         const dev_buf& staging) {
+    double* acc_dev = acc;
+    const size_t img_bytes = P.bytes.staging;
+    if (!R.accum_on_device) {
+        acc_dev = static_cast<double*>(staging.p);
+        HIPCHK(hipMemcpyAsync(acc_dev, acc, img_bytes, hipMemcpyHostToDevice, st));
     }
-    for (auto& p : shade_ev) {
-        HIPCHK(hipEventElapsedTime(&ms, h->events[p.first], h->events[p.second]));
-        stats.ms_shade += ms;
-    }
+    hipLaunchKernelGGL(k_emit, dim3(std::min<uint64_t>((P.npix + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st, sums,
+                       (uint32_t)P.npix, R.nx, R.row_begin, P.row_step, acc_dev);
+    HIPCHK(hipGetLastError());
+    if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(acc, acc_dev, img_bytes, hipMemcpyDeviceToHost, st));
+    return RTW_OK;
+}
+
+// The profiling builds' reports of a finished call (RTW_PROF, RTW_PROF_WALK;
+// nothing in the product build).
+int print_profile(const rtw_stats& stats) {
 #ifdef RTW_PROF_WALK
     {
         static unsigned long long w[32][64];
@@ -2800,11 +2626,124 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
         HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_cls), cl, sizeof cl));
     }
 #endif
+    (void)stats;
+    return RTW_OK;
+}
+
+}  // namespace
+
+// The render of rtw_render_accumulate and, with accum_sq set, of
+// rtw_render_accumulate_moments (rtw_noise.h): the same launches, allocations
+// and copies, except that k_reduce_moments takes k_reduce's place and a
+// second k_emit adds the sums of squares.  With accum_sq null nothing here
+// differs from the plain render.
+static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                             double* accum_rgb, double* accum_sq, rtw_stats* out_stats) {
+    const rtw_render_params& R = *prm;
+    // the call's plan: refusals, sizes, cameras and job fields (render_plan.h)
+    call_plan P;
+    if (int rc = rtw_plan_call(R, *camera, h->facts, accum_rgb, accum_sq, pass_budget_samples(),
+                               RTW_STRICT_RADIANCE ? h->cus : 0, &P))
+        return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (R.accum_on_device) {
+        if (int rc = rtw_check_device_ptr(accum_rgb, h->device, "rtw_render_accumulate")) return rc;
+        if (accum_sq)
+            if (int rc = rtw_check_device_ptr(accum_sq, h->device, "rtw_render_accumulate_moments")) return rc;
+    }
+    hipStream_t st = h->stream;
+    rtw_stats stats;
+    std::memset(&stats, 0, sizeof stats);
+    if (P.noop) {
+        stats.samples = P.samples;
+        if (out_stats) *out_stats = stats;
+        return RTW_OK;
+    }
+
+    // execution form: persistent (paths in registers, one launch per pass)
+    // unless RTW_MODE=wavefront or no persistent instantiation covers the
+    // scene (rtw_select.h; planning launches nothing); the strict build
+    // refuses the other forms here, before any allocation or launch
+    // fp32 fast mode: its own persistent kernel (rtw_fast.h), same passes,
+    // radiance records and ordered per-pixel reduction
+    if (P.fast && !fast_image_ok(h))
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "precision fp32 with image textures covers list and world-BVH scenes only "
+                                             "(this scene has media or group BVHs): render it in fp64");
+    plan_t plan;
+    if (int rc = plan_render(h, P.pin, P.fast, &plan)) return rc;
+    const bool persistent = plan.c.persistent();
+    if (RTW_STRICT_RADIANCE && !persistent)
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders with the persistent kernel only "
+                                             "(RTW_MODE=wavefront or a scene without a persistent instantiation)");
+
+    if (int rc = ensure_buffers(h, P.bytes, accum_sq != nullptr)) return rc;
+    wave_pool W{rtw_carve_paths<paths_t>(h->pool[0].p, P.pool), rtw_carve_paths<paths_t>(h->pool[1].p, P.pool),
+                rtw_carve_fresh<fresh_t>(h->fresh.p, P.pool), static_cast<double*>(h->hits.p),
+                reinterpret_cast<int32_t*>(static_cast<char*>(h->hits.p) + P.hits_id_off), P.pool};
+    ctrs_t* C = static_cast<ctrs_t*>(h->ctrs.p);
+    double* run = static_cast<double*>(h->run.p);
+    double* run2 = accum_sq ? static_cast<double*>(h->run2.p) : nullptr;
+    HIPCHK(hipMemsetAsync(run, 0, P.bytes.run, st));
+    if (run2) HIPCHK(hipMemsetAsync(run2, 0, P.bytes.run2, st));
+    HIPCHK(hipMemsetAsync(C, 0, sizeof(ctrs_t), st));
+
+    // the camera (cam_host lives until the copy ran) and, after it, the
+    // device's own reciprocals of nx and ny
+    h->cam_host = P.cam_dev;
+    HIPCHK(hipMemcpyAsync(h->camera.p, &h->cam_host, sizeof(rtw_camera_desc), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_recips, dim3(1), dim3(64), 0, st,
+                       reinterpret_cast<double*>(static_cast<char*>(h->camera.p) + sizeof(rtw_camera_desc)), R.nx, R.ny);
+    HIPCHK(hipGetLastError());
+
+    call_events E(h, R.collect_kernel_times);
+    hipEvent_t ev_begin = event_at(h, E.ev++), ev_end = event_at(h, E.ev++);
+    if (!ev_begin || !ev_end) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
+    HIPCHK(hipEventRecord(ev_begin, st));
+    job_t J = make_job(h, P, R);
+    fast_args FA = make_fast_args(h, P);
+    for (uint64_t done = 0; done < (uint64_t)P.spp_count; done += P.pass_spp) {
+        const call_pass pass = rtw_plan_pass(P, R, done);
+        set_pass(J, pass);
+        if (persistent) {
+            hipLaunchKernelGGL(k_fill, dim3(1), dim3(kBlock), 0, st, W.A, C, 0u);  // reset the queue
+            FA.J = J;
+            if (int rc = E.timed(E.time_isect, [&] { launch_persistent(plan, h, st, J, C, FA); })) return rc;
+            HIPCHK(hipGetLastError());
+            stats.launches_intersect++;
+            stats.iterations++;
+        } else if (int rc = wavefront_pass(h, plan, J, pass, W, E, stats)) {
+            return rc;
+        }
+        launch_reduce(st, P.fast, J.L, P.npix, pass.spp_pass, run, run2);  // (the wavefront form is fp64 only)
+        HIPCHK(hipGetLastError());
+        stats.samples += J.total;
+    }
+
+    if (int rc = emit(st, P, R, accum_rgb, run, h->accum)) return rc;
+    if (accum_sq)
+        if (int rc = emit(st, P, R, accum_sq, run2, h->accum_sq)) return rc;
+    HIPCHK(hipMemcpyAsync(&h->host_ctrs[63], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(ev_end, st));
+    HIPCHK(hipStreamSynchronize(st));
+
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end));
+    stats.ms_total = ms;
+    for (int k = 0; k < 8; ++k) stats.segments += h->host_ctrs[63].segments[k].v;
+    for (auto& p : E.isect_ev) {
+        HIPCHK(hipEventElapsedTime(&ms, h->events[p.first], h->events[p.second]));
+        stats.ms_intersect += ms;
+    }
+    for (auto& p : E.shade_ev) {
+        HIPCHK(hipEventElapsedTime(&ms, h->events[p.first], h->events[p.second]));
+        stats.ms_shade += ms;
+    }
+    if (int rc = print_profile(stats)) return rc;
     // algorithmic traversal bytes: 56 B ray in +
     // 12 B hit out per world query, whatever the execution form (k_persist
     // keeps both in registers; k_segment / k_intersect stream them)
     // (fp32 fast mode: 7 x 4 B ray in, 4 + 4 B hit out = 36 B)
-    stats.bytes_intersect = (fast ? 36.0 : 68.0) * (double)stats.segments;
+    stats.bytes_intersect = (P.fast ? 36.0 : 68.0) * (double)stats.segments;
     if (out_stats) *out_stats = stats;
     return RTW_OK;
 }

@@ -146,11 +146,34 @@ constexpr std::array kSegmentList{inst{0, SF_IMG_ALL, false}, inst{F_WBVH, SF_IM
                                   inst{0, SF_DIEL, true},     inst{0, SF_METAL | SF_DIEL, true},
                                   inst{0, SF_ALL, true},      inst{0, SF_ALL, false},
                                   inst{F_WBVH, SF_ALL, false}, inst{F_WBVH, SF_ALL, true}};
+// The split pair.  k_shade<m, l> (f = -1: no feature argument) ...
+constexpr std::array kShadeList{inst{-1, SF_DIEL, true},
+                                inst{-1, SF_DIEL, false},
+                                inst{-1, SF_METAL | SF_DIEL, true},
+                                inst{-1, SF_METAL | SF_DIEL, false},
+                                inst{-1, SF_NOISE, true},
+                                inst{-1, SF_NOISE, false},
+                                inst{-1, SF_ALL, true},
+                                inst{-1, SF_IMG_ALL, false},  // (no LDS form for image scenes: select_fp64)
+                                inst{-1, SF_ALL, false}};
+// ... and k_intersect<f>: one traversal kernel per scene-feature combination
+// (a world BVH never coexists with media: validate_desc)
+constexpr std::array kIntersectList{inst{0, -1, false},      inst{F_MEDIA, -1, false},
+                                    inst{F_WBVH, -1, false}, inst{F_GBVH, -1, false},
+                                    inst{F_MEDIA | F_GBVH, -1, false}, inst{F_WBVH | F_GBVH, -1, false}};
 #else
 // experiment builds (scripts/ru_kernel.sh): one persistent kernel only
 constexpr std::array kPersistList{inst{RTW_SUBSET_F, RTW_SUBSET_M, RTW_SUBSET_L}};
 constexpr std::array<inst, 0> kSegmentList{};
+constexpr std::array kShadeList{inst{-1, SF_ALL, false}};
+constexpr std::array kIntersectList{inst{F_MEDIA | F_GBVH, -1, false}};
 #endif
+// what a split choice without a row of its own runs: every material with the
+// scene read through the caches (no LDS bytes), the traversal of everything
+constexpr inst kShadeFallback{-1, SF_ALL, false};
+constexpr inst kIntersectFallback{F_MEDIA | F_GBVH, -1, false};
+static_assert(index_of(kShadeList, kShadeFallback) >= 0 && index_of(kIntersectList, kIntersectFallback) >= 0,
+              "the split pair's fallback rows are instantiated");
 
 // k_fast<f, l> and k_fast_sort<f, l> (l: the scene's fp32 shading data in LDS)
 #ifndef RTW_SUBSET_FAST
@@ -199,7 +222,7 @@ enum class kform { persist_sort, persist, persist_lst, segment, split, fast, fas
 
 struct kernel_choice {
     kform form;
-    inst id;  // the template arguments; split: {features, shade set, LDS shading} of k_intersect / k_shade
+    inst id;  // the template arguments; split: {features, shade set, LDS shading}, the rows by split_resolve
     std::string name;
     bool persistent() const { return form != kform::segment && form != kform::split; }
 };
@@ -251,6 +274,18 @@ inline kernel_choice select_fp64(const select_in& s) {
     if (!s.env.split && index_of(kSegmentList, seg) >= 0)
         return {kform::segment, seg, kname("k_segment", seg.f, seg.m, seg.l)};
     return {kform::split, seg, kname("k_intersect", s.features, -1)};
+}
+
+// The rows a split choice launches: kernel_choice::id names {features, shade
+// set, LDS shading} as selection wants them, these are the instantiations
+// that run.  k_shade stages the scene's shading data in LDS exactly when
+// shade.l (the fallback row reads it through the caches).
+struct split_rows {
+    inst intersect, shade;
+};
+inline split_rows split_resolve(const inst& id) {
+    const inst i{id.f, -1, false}, s{-1, id.m, id.l};
+    return {index_of(kIntersectList, i) >= 0 ? i : kIntersectFallback, index_of(kShadeList, s) >= 0 ? s : kShadeFallback};
 }
 
 // fp32 fast mode: always persistent (RTW_MODE and RTW_SPLIT do not apply).

@@ -3,7 +3,10 @@ walks select_fp64 / select_fp32 over the grids of
 tests/golden/kernel_selection.json -- the names the launch probes gave before
 selection became a function of its own -- and every row must be equal.  The
 program also fails when a choice has no entry in the instantiation lists the
-launch tables are built from."""
+launch tables are built from; for a split choice (k_intersect + k_shade), when
+the rows split_resolve gives are not listed or are not the instantiations the
+launch switches named before the pair came from the tables (their case labels
+and default rows, written out in the program)."""
 import json
 import subprocess
 from pathlib import Path
