@@ -438,7 +438,8 @@ static v3 texture_value(const rtw_scene_desc* S, int id, v3 p) {
         double sines = O_SIN_TEX(10.0 * p.x) * O_SIN_TEX(10.0 * p.y) * O_SIN_TEX(10.0 * p.z);
         return texture_value(S, sines < 0 ? t->odd : t->even, p);
     }
-    default: { /* texture.h:57-68: vec3(1,1,1) * 0.5f * (1 + sin(scale*p.z + 10*turb(p))) */
+    default: { /* RTW_TEX_NOISE (the render entry points refuse every other kind), texture.h:57-68:
+                  vec3(1,1,1) * 0.5f * (1 + sin(scale*p.z + 10*turb(p))) */
         double pp[3] = {p.x, p.y, p.z};
         double s = 1 + O_SIN_TEX(t->scale * p.z + 10 * rtw_oracle_turb(S, pp));
         double v = (1.0 * (double)0.5f) * s;
@@ -652,6 +653,21 @@ static v3 sample(const rtw_scene_desc* S, const rtw_camera_desc* cam, int nx, in
     return color(S, &r, max_depth, &g, tc);
 }
 
+/* texture_value implements constant, checker and noise: any other kind (an
+ * image texture), or a noise texture without the Perlin tables, makes a scene
+ * this restatement cannot shade (Normal mode reads no texture and renders
+ * such a scene) */
+static int textures_ok(const rtw_scene_desc* S) {
+    if (S->has_perlin && (!S->perlin_ranvec || !S->perlin_perm)) return 0;
+    if (S->render_type == RTW_RENDER_NORMAL) return 1;
+    for (int k = 0; k < S->n_textures; k++) {
+        const int type = S->textures[k].type;
+        if (type != RTW_TEX_CONSTANT && type != RTW_TEX_CHECKER && type != RTW_TEX_NOISE) return 0;
+        if (type == RTW_TEX_NOISE && !S->has_perlin) return 0;
+    }
+    return 1;
+}
+
 /* Rows row_begin, row_begin + row_stride, ... (row_count of them), one
  * OpenMP task per row: the bounded CPU sample bench.py times (every
  * stride-th row of the image) in one multithreaded call. */
@@ -660,7 +676,7 @@ int rtw_oracle_render_strided(const rtw_scene_desc* S, const rtw_camera_desc* ca
                               uint64_t seed, int threads, double* sums, uint64_t* segments) {
     if (!S || !cam || !sums || nx <= 0 || ny <= 0 || row_stride <= 0 || row_count < 0) return -1;
     if (row_count > 0 && (row_begin < 0 || row_begin + (int64_t)(row_count - 1) * row_stride >= ny)) return -1;
-    if (S->has_perlin && (!S->perlin_ranvec || !S->perlin_perm)) return -1;
+    if (!textures_ok(S)) return -1;
     uint64_t seg_total = 0;
 #ifdef _OPENMP
     if (threads > 0) omp_set_num_threads(threads);
@@ -693,6 +709,7 @@ int rtw_oracle_render(const rtw_scene_desc* S, const rtw_camera_desc* cam, int n
 
 int rtw_oracle_trace(const rtw_scene_desc* S, const rtw_camera_desc* cam, int nx, int ny, int i, int j, int s,
                      int max_depth, uint64_t seed, double* radiance3, double* seg_rows, int max_seg) {
+    if (!S || !cam || !radiance3 || !textures_ok(S)) return -1;
     trace_ctx tc = {seg_rows, max_seg, 0, 0};
     v3 L = sample(S, cam, nx, ny, i, j, s, max_depth, seed, &tc);
     radiance3[0] = L.x, radiance3[1] = L.y, radiance3[2] = L.z;

@@ -79,9 +79,22 @@ public:
     static std::shared_ptr<image_texture::byte_array> test_image(int which, int& nx, int& ny);
 };
 
+// Test scenes for the converged fp32-vs-fp64 comparison
+// (tests/test_gpu_fp32_probes.py), one shading feature each under bounded
+// radiance: `kind` is one of "rect_light", "sphere_light",
+// "far_sphere_light", "default_light", "glass", "metal", "medium", "motion",
+// "textures" (scenes.cpp says what each holds).  Any other kind leaves the
+// scene empty; make_builtin_scene refuses it.
+class probe_scene : public scene {
+public:
+    probe_scene(double aspect, const std::string& kind);
+    static bool has_kind(const std::string& kind);
+};
+
 // Builds a scene by name ("cornell_box", "random_balls", "dielectric",
 // "light_sample", "book2_final", "nested", "nested_plain", "textured",
-// "grouped", "grouped_world");
+// "grouped", "grouped_world", and the test scenes "probe_<kind>" of
+// probe_scene);
 // nullptr for an unknown name.
 std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect);
 

@@ -399,7 +399,183 @@ grouped_scene::grouped_scene(double aspect, bool extra) {
     cam = look(vec3(3.0, 3.5, 10.0), vec3(0.0, 0.6, 0.0), 35.0, aspect, 0.0, 10.0);
 }
 
+// ---------------------------------------------------------------- probes
+// Test scenes for the converged fp32-vs-fp64 comparison: one shading feature
+// each, filling the frame, with bounded radiance (a gradient sky, or lights
+// reached through the light list) so that per-pixel means converge quickly.
+// Not in the reference; built from its classes.  Every kind carries enough
+// objects (or one list of more than eight) that use_bvh builds a BVH.
+namespace {
+// n small Lambertian balls on a ring around `at`, as one translated list
+// (more than eight primitives: a group BVH under use_bvh)
+std::shared_ptr<hittable> pebbles(int n, double ring, double r, const vec3& at) {
+    std::vector<std::shared_ptr<hittable>> v;
+    for (int k = 0; k < n; ++k) {
+        const double a = 2.0 * 3.14159265358979323846 * (k + 0.25) / n;
+        v.push_back(std::make_shared<sphere>(vec3(ring * std::cos(a), 0.0, ring * std::sin(a)), r,
+                                             diffuse(0.3 + 0.05 * (k % 5), 0.6 - 0.04 * (k % 7), 0.35 + 0.03 * (k % 3))));
+    }
+    return std::make_shared<translate>(std::make_shared<hittable_list>(v), at);
+}
+// single balls, one world object each (with the rest, enough for a world BVH)
+void scatter_balls(scene& sc, int n, double ring, double r, double y) {
+    for (int k = 0; k < n; ++k) {
+        const double a = 2.0 * 3.14159265358979323846 * (k + 0.5) / n;
+        sc.Add(std::make_shared<sphere>(vec3(ring * std::cos(a), y, ring * std::sin(a)), r,
+                                        diffuse(0.65 - 0.06 * (k % 4), 0.3 + 0.07 * (k % 5), 0.25 + 0.1 * (k % 3))));
+    }
+}
+std::shared_ptr<hittable> mover(vec3 c0, vec3 c1, double r, mat_ptr m, double t0, double t1) {
+    auto ms = std::make_shared<moving_sphere>(c0, r, m);
+    movement_linear mv;
+    mv.center1 = c1;
+    mv.time0 = t0;
+    mv.time1 = t1;
+    ms->set_movement(mv);
+    return ms;
+}
+const char* const kProbeKinds[] = {"rect_light", "sphere_light", "far_sphere_light", "default_light", "glass",
+                                   "metal",      "medium",       "motion",           "textures"};
+}  // namespace
+
+bool probe_scene::has_kind(const std::string& kind) {
+    for (const char* k : kProbeKinds)
+        if (kind == k) return true;
+    return false;
+}
+
+probe_scene::probe_scene(double aspect, const std::string& kind) {
+    auto white = diffuse(0.73, 0.73, 0.73);
+    auto glass = std::make_shared<dielectric>(1.5);
+    const vec3 up(0.0, 1.0, 0.0);
+
+    if (kind == "rect_light" || kind == "default_light") {
+        // diffuse_light emits where dot(normal, ray) > 0: a flip_normals'd
+        // xz_rect shines upwards.  So the lit surface is a flipped Lambertian
+        // rect above the lamp, seen from below, the lamp behind the camera:
+        // 4:1 sides (a wrong extent shows; the Cornell lamp is nearly
+        // square), a small rotated, translated box and a ring of balls under
+        // the lit surface for shadows and the rects' frames.
+        auto lamp = std::make_shared<xz_rect>(-2.0, 2.0, -0.5, 0.5, 0.0,
+                                              std::make_shared<diffuse_light>(solid(8.0, 8.0, 8.0)));
+        Add(std::make_shared<flip_normals>(lamp));
+        lights->objects.push_back(lamp);
+        Add(std::make_shared<flip_normals>(std::make_shared<xz_rect>(-10.0, 10.0, -10.0, 10.0, 4.0, white)));
+        auto crate = std::make_shared<box>(vec3(0, 0, 0), vec3(0.8, 0.8, 0.8), diffuse(0.6, 0.5, 0.3));
+        Add(std::make_shared<translate>(std::make_shared<rotate_y>(crate, 25.0), vec3(0.8, 3.2, -0.9)));
+        Add(pebbles(10, 2.4, 0.25, vec3(0.0, 3.75, -0.5)));
+        cam = camera(vec3(0.0, 0.6, 3.5), vec3(0.0, 4.0, 0.0), up, 50.0, aspect, 0.0, 5.0, 0.0, 1.0);
+        background_type = BackgroundType::Black;
+        // the second member has no pdf of its own: hittable's default,
+        // direction (1,0,0) with pdf 0 (RTW_LIGHT_DEFAULT).  A quarter of the
+        // bounces draw it and end the path, and under a black background the
+        // lit surface's samples then spread too widely to converge in 2^16
+        // per pixel: this kind has the gradient sky below the surface.
+        if (kind == "default_light") {
+            lights->objects.push_back(std::make_shared<box>(vec3(5, 0, 5), vec3(6, 1, 6), white));
+            background_type = BackgroundType::Gradient;
+        }
+    } else if (kind == "sphere_light" || kind == "far_sphere_light") {
+        // a sphere emits towards the side its normal points away from, so an
+        // emitter seen from outside has a negative radius (sphere.h:71-77).
+        // Near: the cone of directions to it has a half-angle from about 80
+        // degrees under it to about 10 at the frame's edge; it is in view
+        // (constant emission: no tail).  Far: radius / distance = 1/1000, out
+        // of view, emission scaled so that the floor's level is about 1.
+        const bool far_light = kind == "far_sphere_light";
+        Add(std::make_shared<xz_rect>(-10.0, 10.0, -10.0, 10.0, 0.0, white));
+        const double e = far_light ? 1.7e6 : 1.5;
+        auto lamp = std::make_shared<sphere>(far_light ? vec3(400.0, 800.0, 450.0) : vec3(0.0, 1.02, 0.0), -1.0,
+                                             std::make_shared<diffuse_light>(solid(e, e, e)));
+        Add(lamp);
+        lights->objects.push_back(lamp);
+        auto crate = std::make_shared<box>(vec3(0, 0, 0), vec3(0.8, 0.8, 0.8), diffuse(0.6, 0.5, 0.3));
+        Add(std::make_shared<translate>(std::make_shared<rotate_y>(crate, 25.0), vec3(2.0, 0.0, 0.6)));
+        Add(pebbles(10, 3.4, 0.25, vec3(0.0, 0.25, 0.0)));
+        cam = camera(vec3(0.0, 3.0, 9.0), vec3(0.0, 0.5, 0.0), up, 40.0, aspect, 0.0, 9.0, 0.0, 1.0);
+        background_type = BackgroundType::Black;
+    } else if (kind == "glass") {
+        // a glass ball with a hollow shell (radius -0.9 inside radius 1), a
+        // small solid glass ball, a Lambertian ground, gradient sky
+        Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+        Add(std::make_shared<sphere>(vec3(-0.5, 1.0, 0.0), 1.0, glass));
+        Add(std::make_shared<sphere>(vec3(-0.5, 1.0, 0.0), -0.9, glass));
+        Add(std::make_shared<sphere>(vec3(1.4, 0.6, 0.8), 0.6, glass));
+        scatter_balls(*this, 7, 2.6, 0.3, 0.3);
+        cam = camera(vec3(0.0, 1.8, 5.5), vec3(0.2, 0.8, 0.0), up, 32.0, aspect, 0.0, 5.5, 0.0, 1.0);
+    } else if (kind == "metal") {
+        // metal spheres with fuzz 0, 0.3 and 1.0 in front of a metal rect,
+        // gradient sky
+        Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+        Add(std::make_shared<sphere>(vec3(-1.7, 0.8, 0.0), 0.8, std::make_shared<metal>(vec3(0.9, 0.9, 0.9), 0.0)));
+        Add(std::make_shared<sphere>(vec3(0.0, 0.8, 0.0), 0.8, std::make_shared<metal>(vec3(0.8, 0.6, 0.2), 0.3)));
+        Add(std::make_shared<sphere>(vec3(1.7, 0.8, 0.0), 0.8, std::make_shared<metal>(vec3(0.7, 0.8, 0.9), 1.0)));
+        Add(std::make_shared<xy_rect>(-3.0, 3.0, 0.0, 2.4, -1.4, std::make_shared<metal>(vec3(0.85, 0.85, 0.8), 0.05)));
+        scatter_balls(*this, 6, 2.8, 0.3, 0.3);
+        cam = camera(vec3(0.0, 1.6, 6.0), vec3(0.0, 0.9, 0.0), up, 35.0, aspect, 0.0, 6.0, 0.0, 1.0);
+    } else if (kind == "medium") {
+        // a medium over a rotated, translated box (density 0.5) and a denser
+        // one (2) over a sphere inside a glass shell, coloured isotropic
+        // albedo, gradient sky
+        Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+        auto smoke_box = std::make_shared<box>(vec3(0, 0, 0), vec3(2.0, 2.0, 2.0), white);
+        Add(std::make_shared<constant_medium>(
+            std::make_shared<translate>(std::make_shared<rotate_y>(smoke_box, 20.0), vec3(-2.9, 0.0, -0.6)), 0.5,
+            std::make_shared<isotropic>(solid(0.8, 0.3, 0.2))));
+        Add(std::make_shared<sphere>(vec3(1.4, 1.1, 0.0), 1.1, glass));
+        Add(std::make_shared<constant_medium>(std::make_shared<sphere>(vec3(1.4, 1.1, 0.0), 1.0, glass), 2.0,
+                                              std::make_shared<isotropic>(solid(0.2, 0.4, 0.9))));
+        Add(pebbles(10, 3.3, 0.25, vec3(0.0, 0.25, 0.6)));
+        cam = camera(vec3(0.0, 2.0, 7.0), vec3(0.0, 1.0, 0.0), up, 34.0, aspect, 0.0, 7.0, 0.0, 1.0);
+    } else if (kind == "motion") {
+        // every motion class the upload derives (tests/cpp/gpu_user_scene.cpp
+        // motion_scene): a run of y-only movers and static spheres of odd
+        // length, a lamp between the runs, a static sphere at y == 0, an
+        // x-mover, a y-mover at x == 0, movers on [0.2, 0.7], a translated
+        // mover, and a moving sphere among the lights only
+        auto red = diffuse(0.65, 0.05, 0.05);
+        auto light = std::make_shared<diffuse_light>(solid(6.0, 6.0, 6.0));
+        Add(std::make_shared<sphere>(vec3(0.5, -1000, 0.25), 1000, white));
+        for (int k = 0; k < 6; ++k)
+            Add(mover(vec3(-2.5 + k, 0.3, 1.5), vec3(-2.5 + k, 0.3 + 0.1 * k, 1.5), 0.3, k & 1 ? red : white, 0.0, 1.0));
+        Add(std::make_shared<sphere>(vec3(1.7, 0.4, -0.6), 0.4, glass));
+        Add(std::make_shared<sphere>(vec3(-1.2, 0.2, 0.6), 0.2, red));
+        auto lamp = std::make_shared<xz_rect>(-1.0, 1.0, -1.0, 1.0, 4.0, light);
+        Add(std::make_shared<translate>(std::make_shared<flip_normals>(lamp), vec3(0.0, 0.0, 0.0)));
+        lights->objects.push_back(lamp);
+        Add(std::make_shared<sphere>(vec3(-1.8, 0.0, -1.2), 0.35, red));
+        Add(mover(vec3(-0.8, 0.35, -1.4), vec3(-0.5, 0.35, -1.4), 0.35, white, 0.0, 1.0));
+        Add(mover(vec3(0.0, 0.3, -2.0), vec3(0.0, 0.7, -2.0), 0.3, red, 0.0, 1.0));
+        Add(mover(vec3(0.9, 0.3, -2.2), vec3(0.9, 0.9, -2.2), 0.3, white, 0.2, 0.7));
+        Add(mover(vec3(2.0, 0.5, -1.0), vec3(2.3, 0.5, -1.3), 0.3, glass, 0.2, 0.7));
+        Add(std::make_shared<translate>(mover(vec3(0, 0.25, 0), vec3(0, 0.55, 0), 0.25, red, 0.0, 1.0),
+                                        vec3(-0.6, 0.0, 2.4)));
+        lights->objects.push_back(mover(vec3(2.5, 3.0, 2.0), vec3(2.5, 3.2, 2.0), 0.5, light, 0.0, 1.0));
+        cam = camera(vec3(0.0, 2.0, 7.0), vec3(0.0, 0.5, 0.0), up, 40.0, aspect, 0.0, 7.0, 0.0, 1.0);
+    } else if (kind == "textures") {
+        // a checker ground sphere seen from high enough that coordinates in
+        // view reach a few hundred (the checker's sines take thousands of
+        // radians), a marble sphere, a thin lens of aperture 0.3; no image
+        // texture (the oracle has none)
+        tex_ptr dark = solid(0.2, 0.3, 0.1), bright = solid(0.9, 0.9, 0.9);
+        tex_ptr marble = std::make_shared<noise_texture>(4.0);
+        Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0,
+                                     std::make_shared<lambertian>(std::make_shared<checker_texture>(dark, bright))));
+        Add(std::make_shared<sphere>(vec3(0.0, 6.0, 0.0), 6.0, std::make_shared<lambertian>(marble)));
+        for (int k = 0; k < 8; ++k) {
+            const double a = 2.0 * 3.14159265358979323846 * (k + 0.5) / 8;
+            mat_ptr m = diffuse(0.7, 0.3 + 0.05 * k, 0.2);
+            if (k & 1) m = std::make_shared<lambertian>(marble);
+            Add(std::make_shared<sphere>(vec3(11.0 * std::cos(a), 1.5, 11.0 * std::sin(a)), 1.5, m));
+        }
+        const vec3 from(0.0, 22.0, 60.0), at(0.0, 5.0, 0.0);
+        cam = camera(from, at, up, 30.0, aspect, 0.3, (from - at).length(), 0.0, 1.0);
+    }
+}
+
 std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect) {
+    if (name.rfind("probe_", 0) == 0 && probe_scene::has_kind(name.substr(6)))
+        return std::make_unique<probe_scene>(aspect, name.substr(6));
     if (name == "grouped") return std::make_unique<grouped_scene>(aspect);
     if (name == "grouped_world") return std::make_unique<grouped_scene>(aspect, true);
     if (name == "nested") return std::make_unique<nested_scene>(aspect);

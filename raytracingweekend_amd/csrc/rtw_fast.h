@@ -340,9 +340,16 @@ RTW_D void arbitrate_item(const fscene& S, int it, const fray& r, float tmin, fh
 struct slab_rayf {
     f3 inv, oi;  // t = x * inv + oi per axis
 };
+// The inverse of a direction component, kept finite: a zero component (the
+// default light pdf's direction (1,0,0), hittable.h:37) has rcp = inf, then
+// oi = -o * inf, and x * inf + oi is inf - inf = NaN for a bound on the
+// origin's side of zero, which the min / max below read as a missed slab.
+// At 2^96 the products stay finite for coordinates below 2^31 and still
+// exceed every t.
+RTW_D float slab_inv(float d) { return __builtin_amdgcn_fmed3f(rcp(d), -0x1p96f, 0x1p96f); }
 RTW_D slab_rayf make_slab(const fscene& S, const fray& r) {
     slab_rayf s;
-    s.inv = f3{rcp(r.d.x), rcp(r.d.y), rcp(r.d.z)};
+    s.inv = f3{slab_inv(r.d.x), slab_inv(r.d.y), slab_inv(r.d.z)};
     s.oi = f3{-r.o.x * s.inv.x, -r.o.y * s.inv.y, -r.o.z * s.inv.z};
     (void)S;
     return s;
@@ -706,6 +713,22 @@ RTW_D f3 cone_dir(float r1, float z) {  // shared tail of the cosine / sphere-co
     const float sq = fsqrt(__builtin_fmaxf(0.0f, 1 - z * z));
     return f3{cos_rev(r1) * sq, sin_rev(r1) * sq, z};
 }
+// cone_dir(r1, 1 - w) for a small w: sin^2 = w (2 - w), formed before 1 - w
+// rounds (near 1 a float z has steps of 2^-24, and 1 - z z only those)
+RTW_D f3 cone_dir_from_top(float r1, float w) {
+    const float sq = fsqrt(w * (2.0f - w));
+    return f3{cos_rev(r1) * sq, sin_rev(r1) * sq, 1.0f - w};
+}
+// 1 - cos(theta_max) of the cone a sphere of squared radius r2 fills from
+// squared distance d2 (sphere.h:92, :104), as q / (1 + sqrt(1 - q)) with
+// q = r2 / d2: 1 - sqrt(1 - q) cancels (q = 1e-6, a sphere at a thousand
+// radii, keeps three bits of it in a float).  Multiplied through by d2 it is
+// r2 / (d2 + sqrt(d2 (d2 - r2))), one root and one reciprocal; d2 - r2 only
+// has to be good relative to d2.  1 inside the sphere, as the clamped root
+// gives.
+RTW_D float cone_top(float r2, float d2) {
+    return __builtin_fminf(r2 * rcp(d2 + fsqrt(d2 * __builtin_fmaxf(d2 - r2, 0.0f))), 1.0f);
+}
 RTW_D float light_pdf_value(const fscene& S, const rtw_light& L, f3 o, f3 v) {
     const fray r{o, v, kFltMaxF};
     float t;
@@ -719,8 +742,7 @@ RTW_D float light_pdf_value(const fscene& S, const rtw_light& L, f3 o, f3 v) {
     if (L.kind == RTW_LIGHT_SPHERE) {  // sphere.h:88-99
         const prim32& q = S.prims[L.prim];
         if (!sphere_t(q, r, 0.001f, __builtin_inff(), t)) return 0;
-        const float cos_theta_max = fsqrt(__builtin_fmaxf(0.0f, 1 - q.p[9] * rcp(len2(f3{q.p[0], q.p[1], q.p[2]} - o))));
-        return rcp(2 * kPiF * (1.0f - cos_theta_max));
+        return rcp(2 * kPiF * cone_top(q.p[9], len2(f3{q.p[0], q.p[1], q.p[2]} - o)));
     }
     return 0;
 }
@@ -742,8 +764,8 @@ RTW_D f3 mixture_generate(const fscene& S, const onbf& fr, f3 o, uint32_t& rng) 
         const prim32& q = S.prims[L.prim];
         const f3 dir = f3{q.p[0], q.p[1], q.p[2]} - o;
         const float r1 = u01(rng), r2 = u01(rng);
-        const float z = 1 + r2 * (fsqrt(__builtin_fmaxf(0.0f, 1 - q.p[9] * rcp(len2(dir)))) - 1);
-        return local(onb_from_w(dir), cone_dir(r1, z));
+        // z = 1 - r2 (1 - cos_theta_max)
+        return local(onb_from_w(dir), cone_dir_from_top(r1, r2 * cone_top(q.p[9], len2(dir))));
     }
     return f3{1, 0, 0};  // hittable.h:37
 }

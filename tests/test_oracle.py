@@ -53,6 +53,40 @@ def test_oracle_sample_ranges_compose(api):
     assert np.allclose(a + b, full, rtol=1e-13, atol=1e-13)
 
 
+def test_oracle_refuses_a_texture_kind_it_does_not_implement(api):
+    """An image texture (and a noise texture without the Perlin tables) is a
+    malformed scene to the oracle: -1 from every render entry point and
+    nothing written, where texture_value once took the noise branch without
+    its tables."""
+    sd = api.SceneDesc("textured", 4 / 3)
+    assert any(sd.desc.textures[k].type == _abi.RTW_TEX_IMAGE for k in range(sd.desc.n_textures))
+    L = oracle()
+    out = np.full(16 * 12 * 3, 7.0)
+    seg = C.c_uint64(99)
+    args = (16, 12, 0, 12, 0, 128, 50, 1, 0, out.ctypes.data_as(C.c_void_p), C.byref(seg))
+    assert L.rtw_oracle_render(sd.ptr, C.byref(sd.camera), *args) == -1
+    assert L.rtw_oracle_render_strided(sd.ptr, C.byref(sd.camera), 16, 12, 0, 1, 12, 0, 128, 50, 1, 0,
+                                       out.ctypes.data_as(C.c_void_p), C.byref(seg)) == -1
+    rad = (C.c_double * 3)(5.0, 5.0, 5.0)
+    assert L.rtw_oracle_trace(sd.ptr, C.byref(sd.camera), 16, 12, 3, 4, 0, 50, 1, rad, None, 0) == -1
+    assert np.all(out == 7.0) and seg.value == 99 and list(rad) == [5.0, 5.0, 5.0]
+    # Normal mode reads no texture: the same scene renders there
+    dn = _abi.rtw_scene_desc.from_buffer_copy(sd.desc)
+    dn.render_type = _abi.RTW_RENDER_NORMAL
+    normals = np.zeros(16 * 12 * 3)
+    nargs = (16, 12, 0, 12, 0, 2, 50, 1, 0, normals.ctypes.data_as(C.c_void_p), C.byref(seg))
+    assert L.rtw_oracle_render(C.byref(dn), C.byref(sd.camera), *nargs) == 0
+    assert np.all(np.isfinite(normals)) and normals.sum() > 0
+    # a noise texture whose desc carries no tables
+    sn = api.SceneDesc("light_sample", 2.0)
+    d = _abi.rtw_scene_desc.from_buffer_copy(sn.desc)
+    d.has_perlin = 0
+    assert L.rtw_oracle_render(C.byref(d), C.byref(sn.camera), *args) == -1
+    # and the scene itself still renders
+    sums, n = oracle_sums(sn, 8, 4, 2, 50, seed=1)
+    assert n > 0 and np.all(np.isfinite(sums)) and sums.sum() > 0
+
+
 def _canonical_py(state):
     """libstdc++ generate_canonical<double,53>(std::minstd_rand) in Python."""
     R = 2147483646
