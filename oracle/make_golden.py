@@ -10,7 +10,9 @@ Writes, for the parity tests (which must run where the reference is absent):
   render_<case>.npy      per-pixel radiance sums (float64, nx*ny*3)
   renders.json           the cases: scene, size, spp, depth, seed, segments and,
                          for a render in the reference's RenderType::Normal,
-                         "render_type": "normal" (absent: shaded)
+                         "render_type": "normal" (absent: shaded), and, where the
+                         reference's camera was built with another shutter than
+                         the scene's own, "shutter": [t0, t1]
   ppm_<case>.ppm         whole images as the reference writes them
                          (RayTracingWeekend.cpp:235-276: average, gamma 2,
                          clamp, P3 rows ny-1..0, int(255.99f * c))
@@ -32,7 +34,13 @@ OUT = ROOT / "tests" / "golden"
 SCENES = [("cornell_box", 1.0), ("random_balls", 1.5), ("dielectric", 2.0), ("light_sample", 2.0),
           ("book2_final", 1.0), ("nested", 1.0), ("nested_plain", 1.0)]
 
-# (case, scene, nx, ny, spp, depth, seed[, render_type])
+PROBE_KINDS = ["rect_light", "sphere_light", "far_sphere_light", "default_light", "glass", "metal", "medium",
+               "motion", "textures"]
+SCENES += [(f"probe_{kind}", 32 / 24) for kind in PROBE_KINDS]
+NARROW = [0.25, 0.5]  # the shutter of ref_harness.cpp's probe_motion_narrow
+
+# (case, scene, nx, ny, spp, depth, seed[, render_type]); the scene
+# "probe_motion_narrow" is recorded as probe_motion with "shutter": NARROW
 RENDERS = [
     ("cornell_32x32x4_d50", "cornell_box", 32, 32, 4, 50, 0),
     ("cornell_24x24x3_d100", "cornell_box", 24, 24, 3, 100, 5),
@@ -53,6 +61,18 @@ RENDERS = [
     ("random_balls_normal_48x32x4", "random_balls", 48, 32, 4, 50, 1, "normal"),
     ("nested_normal_24x24x4", "nested", 24, 24, 4, 50, 2, "normal"),
     ("book2_final_normal_16x16x2", "book2_final", 16, 16, 2, 50, 3, "normal"),
+]
+# the probe scenes (ours, composed in ref_harness.cpp): one per kind and the
+# narrow shutter, every case with a seed of its own
+RENDERS += [(f"probe_{kind}_32x24x4_d50", f"probe_{kind}", 32, 24, 4, 50, 21 + i)
+            for i, kind in enumerate(PROBE_KINDS)]
+RENDERS += [
+    ("probe_motion_narrow_32x24x4_d50", "probe_motion_narrow", 32, 24, 4, 50, 30),
+    ("probe_medium_32x24x4_d5", "probe_medium", 32, 24, 4, 5, 31),    # cut off inside the media
+    ("probe_glass_32x24x4_d100", "probe_glass", 32, 24, 4, 100, 32),
+    ("probe_motion_normal_32x24x4", "probe_motion", 32, 24, 4, 50, 33, "normal"),
+    ("probe_motion_narrow_normal_32x24x4", "probe_motion_narrow", 32, 24, 4, 50, 34, "normal"),
+    ("probe_textures_24x16x8_d50", "probe_textures", 24, 16, 8, 50, 35),  # more lens and jitter draws per pixel
 ]
 
 # whole-image P3 files (case, scene, nx, ny, spp, depth, seed)
@@ -86,10 +106,13 @@ def main() -> int:
         sums = np.fromfile(path, dtype=np.float64)
         path.unlink()
         np.save(OUT / f"render_{case}.npy", sums)
-        meta.append({"case": case, "scene": scene, "nx": nx, "ny": ny, "spp": spp, "max_depth": depth,
-                     "seed": seed, "segments": info["segments"]})
+        narrow = scene == "probe_motion_narrow"
+        meta.append({"case": case, "scene": "probe_motion" if narrow else scene, "nx": nx, "ny": ny, "spp": spp,
+                     "max_depth": depth, "seed": seed, "segments": info["segments"]})
         if render_type != "shaded":
             meta[-1]["render_type"] = render_type
+        if narrow:
+            meta[-1]["shutter"] = NARROW
     (OUT / "renders.json").write_text(json.dumps(meta, indent=1))
     ppm_meta = []
     for case, scene, nx, ny, spp, depth, seed in PPMS:

@@ -30,6 +30,8 @@
 //          times render() over every row_stride-th row (default: all rows)
 //   perlin                                  Perlin tables + noise/turb samples
 // A scene name "normal:<name>" is <name> with RenderType::Normal.
+// "probe_<kind>" are the probe scenes (probe_ref_scene below), and
+// "probe_motion_narrow" is probe_motion with the camera's shutter [0.25, 0.5].
 #include "rng_inject.h"
 
 #include <cfloat>
@@ -282,6 +284,163 @@ public:
     }
 };
 
+// ---------------------------------------------------------------------------
+// Probe scenes (ours; scenes.cpp probe_scene builds the same with the
+// library's host API): one shading feature each.  The same literals, the same
+// std::cos / std::sin expressions and the same order of Add calls and of
+// lights->objects as there.  `t0`, `t1` are the camera's shutter: [0, 1] in
+// every kind, [0.25, 0.5] for "probe_motion_narrow".
+// ---------------------------------------------------------------------------
+class probe_ref_scene : public scene {
+    typedef std::shared_ptr<material> mat_ptr;
+    typedef std::shared_ptr<texture> tex_ptr;
+    static tex_ptr solid(double r, double g, double b) { return std::make_shared<constant_texture>(vec3(r, g, b)); }
+    static mat_ptr diffuse(double r, double g, double b) { return std::make_shared<lambertian>(solid(r, g, b)); }
+    // Every angle of the rings reaches std::cos and std::sin through a volatile
+    // read of its own, so that libm's cos and sin evaluate them at run time,
+    // as in the library's build of scenes.cpp.  g++ -O2 otherwise merges
+    // cos(a) and sin(a) into one sincos(a), and glibc's sincos is one ulp off
+    // its sin at 2 pi 8.25 / 10: a pebble's centre then differs in its last
+    // bit, and with it a few pixels of the render.
+    static double at_run_time(double a) {
+        volatile double v = a;
+        return v;
+    }
+    static std::shared_ptr<hittable> pebbles(int n, double ring, double r, const vec3& at) {
+        std::vector<std::shared_ptr<hittable>> v;
+        for (int k = 0; k < n; ++k) {
+            const double a = 2.0 * 3.14159265358979323846 * (k + 0.25) / n;
+            v.push_back(std::make_shared<sphere>(
+                vec3(ring * std::cos(at_run_time(a)), 0.0, ring * std::sin(at_run_time(a))), r,
+                diffuse(0.3 + 0.05 * (k % 5), 0.6 - 0.04 * (k % 7), 0.35 + 0.03 * (k % 3))));
+        }
+        return std::make_shared<translate>(std::make_shared<hittable_list>(v), at);
+    }
+    void scatter_balls(int n, double ring, double r, double y) {
+        for (int k = 0; k < n; ++k) {
+            const double a = 2.0 * 3.14159265358979323846 * (k + 0.5) / n;
+            Add(std::make_shared<sphere>(vec3(ring * std::cos(at_run_time(a)), y, ring * std::sin(at_run_time(a))), r,
+                                         diffuse(0.65 - 0.06 * (k % 4), 0.3 + 0.07 * (k % 5), 0.25 + 0.1 * (k % 3))));
+        }
+    }
+    static std::shared_ptr<hittable> mover(vec3 c0, vec3 c1, double r, mat_ptr m, double t0, double t1) {
+        auto ms = std::make_shared<moving_sphere>(c0, r, m);
+        movement_linear mv;
+        mv.center1 = c1;
+        mv.time0 = t0;
+        mv.time1 = t1;
+        ms->set_movement(mv);
+        return ms;
+    }
+
+public:
+    static bool has_kind(const std::string& kind) {
+        for (const char* k : {"rect_light", "sphere_light", "far_sphere_light", "default_light", "glass", "metal",
+                              "medium", "motion", "textures"})
+            if (kind == k) return true;
+        return false;
+    }
+
+    probe_ref_scene(double aspect, const std::string& kind, double t0 = 0.0, double t1 = 1.0) : scene() {
+        auto white = diffuse(0.73, 0.73, 0.73);
+        auto glass = std::make_shared<dielectric>(1.5);
+        const vec3 up(0.0, 1.0, 0.0);
+
+        if (kind == "rect_light" || kind == "default_light") {
+            auto lamp = std::make_shared<xz_rect>(-2.0, 2.0, -0.5, 0.5, 0.0,
+                                                  std::make_shared<diffuse_light>(solid(8.0, 8.0, 8.0)));
+            Add(std::make_shared<flip_normals>(lamp));
+            lights->objects.push_back(lamp);
+            Add(std::make_shared<flip_normals>(std::make_shared<xz_rect>(-10.0, 10.0, -10.0, 10.0, 4.0, white)));
+            auto crate = std::make_shared<box>(vec3(0, 0, 0), vec3(0.8, 0.8, 0.8), diffuse(0.6, 0.5, 0.3));
+            Add(std::make_shared<translate>(std::make_shared<rotate_y>(crate, 25.0), vec3(0.8, 3.2, -0.9)));
+            Add(pebbles(10, 2.4, 0.25, vec3(0.0, 3.75, -0.5)));
+            cam = camera(vec3(0.0, 0.6, 3.5), vec3(0.0, 4.0, 0.0), up, 50.0, aspect, 0.0, 5.0, t0, t1);
+            background_type = BackgroundType::Black;
+            if (kind == "default_light") {
+                lights->objects.push_back(std::make_shared<box>(vec3(5, 0, 5), vec3(6, 1, 6), white));
+                background_type = BackgroundType::Gradient;
+            }
+        } else if (kind == "sphere_light" || kind == "far_sphere_light") {
+            const bool far_light = kind == "far_sphere_light";
+            Add(std::make_shared<xz_rect>(-10.0, 10.0, -10.0, 10.0, 0.0, white));
+            const double e = far_light ? 1.7e6 : 1.5;
+            auto lamp = std::make_shared<sphere>(far_light ? vec3(400.0, 800.0, 450.0) : vec3(0.0, 1.02, 0.0), -1.0,
+                                                 std::make_shared<diffuse_light>(solid(e, e, e)));
+            Add(lamp);
+            lights->objects.push_back(lamp);
+            auto crate = std::make_shared<box>(vec3(0, 0, 0), vec3(0.8, 0.8, 0.8), diffuse(0.6, 0.5, 0.3));
+            Add(std::make_shared<translate>(std::make_shared<rotate_y>(crate, 25.0), vec3(2.0, 0.0, 0.6)));
+            Add(pebbles(10, 3.4, 0.25, vec3(0.0, 0.25, 0.0)));
+            cam = camera(vec3(0.0, 3.0, 9.0), vec3(0.0, 0.5, 0.0), up, 40.0, aspect, 0.0, 9.0, t0, t1);
+            background_type = BackgroundType::Black;
+        } else if (kind == "glass") {
+            Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+            Add(std::make_shared<sphere>(vec3(-0.5, 1.0, 0.0), 1.0, glass));
+            Add(std::make_shared<sphere>(vec3(-0.5, 1.0, 0.0), -0.9, glass));
+            Add(std::make_shared<sphere>(vec3(1.4, 0.6, 0.8), 0.6, glass));
+            scatter_balls(7, 2.6, 0.3, 0.3);
+            cam = camera(vec3(0.0, 1.8, 5.5), vec3(0.2, 0.8, 0.0), up, 32.0, aspect, 0.0, 5.5, t0, t1);
+        } else if (kind == "metal") {
+            Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+            Add(std::make_shared<sphere>(vec3(-1.7, 0.8, 0.0), 0.8,
+                                         std::make_shared<metal>(vec3(0.9, 0.9, 0.9), 0.0)));
+            Add(std::make_shared<sphere>(vec3(0.0, 0.8, 0.0), 0.8, std::make_shared<metal>(vec3(0.8, 0.6, 0.2), 0.3)));
+            Add(std::make_shared<sphere>(vec3(1.7, 0.8, 0.0), 0.8, std::make_shared<metal>(vec3(0.7, 0.8, 0.9), 1.0)));
+            Add(std::make_shared<xy_rect>(-3.0, 3.0, 0.0, 2.4, -1.4,
+                                          std::make_shared<metal>(vec3(0.85, 0.85, 0.8), 0.05)));
+            scatter_balls(6, 2.8, 0.3, 0.3);
+            cam = camera(vec3(0.0, 1.6, 6.0), vec3(0.0, 0.9, 0.0), up, 35.0, aspect, 0.0, 6.0, t0, t1);
+        } else if (kind == "medium") {
+            Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+            auto smoke_box = std::make_shared<box>(vec3(0, 0, 0), vec3(2.0, 2.0, 2.0), white);
+            Add(std::make_shared<constant_medium>(
+                std::make_shared<translate>(std::make_shared<rotate_y>(smoke_box, 20.0), vec3(-2.9, 0.0, -0.6)), 0.5,
+                std::make_shared<isotropic>(solid(0.8, 0.3, 0.2))));
+            Add(std::make_shared<sphere>(vec3(1.4, 1.1, 0.0), 1.1, glass));
+            Add(std::make_shared<constant_medium>(std::make_shared<sphere>(vec3(1.4, 1.1, 0.0), 1.0, glass), 2.0,
+                                                  std::make_shared<isotropic>(solid(0.2, 0.4, 0.9))));
+            Add(pebbles(10, 3.3, 0.25, vec3(0.0, 0.25, 0.6)));
+            cam = camera(vec3(0.0, 2.0, 7.0), vec3(0.0, 1.0, 0.0), up, 34.0, aspect, 0.0, 7.0, t0, t1);
+        } else if (kind == "motion") {
+            auto red = diffuse(0.65, 0.05, 0.05);
+            auto light = std::make_shared<diffuse_light>(solid(6.0, 6.0, 6.0));
+            Add(std::make_shared<sphere>(vec3(0.5, -1000, 0.25), 1000, white));
+            for (int k = 0; k < 6; ++k)
+                Add(mover(vec3(-2.5 + k, 0.3, 1.5), vec3(-2.5 + k, 0.3 + 0.1 * k, 1.5), 0.3,
+                          k & 1 ? mat_ptr(red) : mat_ptr(white), 0.0, 1.0));
+            Add(std::make_shared<sphere>(vec3(1.7, 0.4, -0.6), 0.4, glass));
+            Add(std::make_shared<sphere>(vec3(-1.2, 0.2, 0.6), 0.2, red));
+            auto lamp = std::make_shared<xz_rect>(-1.0, 1.0, -1.0, 1.0, 4.0, light);
+            Add(std::make_shared<translate>(std::make_shared<flip_normals>(lamp), vec3(0.0, 0.0, 0.0)));
+            lights->objects.push_back(lamp);
+            Add(std::make_shared<sphere>(vec3(-1.8, 0.0, -1.2), 0.35, red));
+            Add(mover(vec3(-0.8, 0.35, -1.4), vec3(-0.5, 0.35, -1.4), 0.35, white, 0.0, 1.0));
+            Add(mover(vec3(0.0, 0.3, -2.0), vec3(0.0, 0.7, -2.0), 0.3, red, 0.0, 1.0));
+            Add(mover(vec3(0.9, 0.3, -2.2), vec3(0.9, 0.9, -2.2), 0.3, white, 0.2, 0.7));
+            Add(mover(vec3(2.0, 0.5, -1.0), vec3(2.3, 0.5, -1.3), 0.3, glass, 0.2, 0.7));
+            Add(std::make_shared<translate>(mover(vec3(0, 0.25, 0), vec3(0, 0.55, 0), 0.25, red, 0.0, 1.0),
+                                            vec3(-0.6, 0.0, 2.4)));
+            lights->objects.push_back(mover(vec3(2.5, 3.0, 2.0), vec3(2.5, 3.2, 2.0), 0.5, light, 0.0, 1.0));
+            cam = camera(vec3(0.0, 2.0, 7.0), vec3(0.0, 0.5, 0.0), up, 40.0, aspect, 0.0, 7.0, t0, t1);
+        } else if (kind == "textures") {
+            tex_ptr dark = solid(0.2, 0.3, 0.1), bright = solid(0.9, 0.9, 0.9);
+            tex_ptr marble = std::make_shared<noise_texture>(4.0);
+            Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0,
+                                         std::make_shared<lambertian>(std::make_shared<checker_texture>(dark, bright))));
+            Add(std::make_shared<sphere>(vec3(0.0, 6.0, 0.0), 6.0, std::make_shared<lambertian>(marble)));
+            for (int k = 0; k < 8; ++k) {
+                const double a = 2.0 * 3.14159265358979323846 * (k + 0.5) / 8;
+                mat_ptr m = diffuse(0.7, 0.3 + 0.05 * k, 0.2);
+                if (k & 1) m = std::make_shared<lambertian>(marble);
+                Add(std::make_shared<sphere>(vec3(11.0 * std::cos(at_run_time(a)), 1.5, 11.0 * std::sin(at_run_time(a))), 1.5, m));
+            }
+            const vec3 from(0.0, 22.0, 60.0), at(0.0, 5.0, 0.0);
+            cam = camera(from, at, up, 30.0, aspect, 0.3, (from - at).length(), t0, t1);
+        }
+    }
+};
+
 // "normal:<scene>": the scene with the reference's RenderType::Normal
 // (RayTracingWeekend.cpp:135-136).  render_type is a protected member with
 // no setter, so a derived class reaches it.
@@ -295,6 +454,9 @@ static scene* make_scene(const std::string& name, double aspect) {
         render_type_access::set(s, RenderType::Normal);
         return s;
     }
+    if (name == "probe_motion_narrow") return new probe_ref_scene(aspect, "motion", 0.25, 0.5);
+    if (name.rfind("probe_", 0) == 0 && probe_ref_scene::has_kind(name.substr(6)))
+        return new probe_ref_scene(aspect, name.substr(6));
     if (name == "grouped") return new grouped_scene(aspect);
     if (name == "grouped_world") return new grouped_scene(aspect, true);
     if (name == "nested") return new nested_scene(aspect);
@@ -513,6 +675,23 @@ static void dump_scene(scene* sc) {
     std::string lights = sc->GetLights() ? dp.obj(sc->GetLights().get()) : "null";
     const camera& c = sc->GetCamera();
     printf("{\"world\":%s,\n\"lights\":%s,\n", world.c_str(), lights.c_str());
+    // A light-list member of a class that does not override pdf_value / random
+    // (only xz_rect, sphere_base and hittable_list do: hittable.h:208-228,
+    // sphere.h:88-108, hittable_list.h:44-59) samples with hittable's defaults
+    // (hittable.h:36-37).  Said per member, and only where there is one, so
+    // the dumps of scenes without such a member keep their bytes.
+    if (sc->GetLights()) {
+        std::string pdfs;
+        bool any_default = false;
+        for (const auto& o : sc->GetLights()->objects) {
+            const hittable* h = o.get();
+            const bool own = dynamic_cast<const xz_rect*>(h) || dynamic_cast<const sphere*>(h) ||
+                             dynamic_cast<const moving_sphere*>(h) || dynamic_cast<const hittable_list*>(h);
+            any_default |= !own;
+            pdfs += std::string(pdfs.empty() ? "" : ",") + (own ? "\"own\"" : "\"default\"");
+        }
+        if (any_default) printf("\"light_pdf\":[%s],\n", pdfs.c_str());
+    }
     printf("\"materials\":[");
     for (size_t i = 0; i < dp.mat_json.size(); i++) printf("%s%s", i ? "," : "", dp.mat_json[i].c_str());
     printf("],\n\"textures\":[");

@@ -165,6 +165,24 @@ bool true_box(const hittable* h, double t0, double t1, aabb& out) {
         out = aabb(lo, hi);
         return true;
     }
+    if (auto ms = dynamic_cast<const moving_sphere*>(h)) {
+        // movement_linear::bounding_box (sphere.h:27-33) ignores t0, t1 and
+        // bounds the sphere at center and center1, but center() extrapolates
+        // outside the movement's [time0, time1] (sphere.h:22-25): a ray at a
+        // time of the shutter outside that interval meets the sphere outside
+        // that box.  The centre moves along a line, so its extremes over the
+        // shutter are the centres at t0 and t1 (as the flattener's prim_box).
+        const double r = std::fabs(ms->radius);
+        vec3 lo(inf), hi(-inf);
+        for (const vec3& c : {ms->center, ms->movement.center1, ms->movement.center(ms->center, t0),
+                              ms->movement.center(ms->center, t1)})
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::fmin(lo[a], c[a] - r);
+                hi[a] = std::fmax(hi[a], c[a] + r);
+            }
+        out = aabb(lo, hi);
+        return true;
+    }
     if (!h->bounding_box(t0, t1, out)) return false;
     // a negative radius (hollow glass) gives sphere boxes with min > max
     vec3 lo = out.min(), hi = out.max();

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """What rtw_scene_query reports (kernel, kernel_fast, bvh_lds_nodes,
-shade_lds_bytes) for every scene of tests/golden/scene_*.json, flat and with
+shade_lds_bytes) for every scene of tests/golden/scene_*.json but the probe
+scenes (scene_probe_*.json: their kernels are listed, with the renders that
+drive them, in profiles/probe_reference/kernels_by_case.txt), flat and with
 BVHs, under the environments that steer kernel selection: {}, RTW_MODE=wavefront
 and wavefront + RTW_SPLIT=1 in this process (read at every call), RTW_SORT=0
 and RTW_SORT=1 in one child process each (read once).  Prints one JSON
@@ -28,6 +30,8 @@ def query_all():
     out = {}
     for p in sorted((ROOT / "tests" / "golden").glob("scene_*.json")):
         name, aspect = p.stem[len("scene_"):], json.loads(p.read_text()).get("aspect")
+        if name.startswith("probe_"):
+            continue
         for bvh in (False, True) if aspect else ():  # (this script's own output is no scene dump)
             ds = render.DeviceScene(render.SceneDesc(name, aspect, use_bvh=bvh))
             try:

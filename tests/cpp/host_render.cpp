@@ -8,11 +8,13 @@
 // bit for bit with tests/golden/render_*.npy, which the reference's own
 // classes produced under the same streams (tests/test_host_eval.py).
 //
-//   host_render <scene> <nx> <ny> <spp> <depth> <seed> <flat|bvh> <out.bin>
+//   host_render <scene> <nx> <ny> <spp> <depth> <seed> <flat|bvh> <out.bin> [<time0> <time1>]
 //     out.bin: nx*ny*3 doubles (per-pixel radiance sums in sample order, row
 //     j = 0 at the bottom), then one uint64: the world traversals (hit calls)
 //
 // A scene name "normal:<name>" is <name> with RenderType::Normal (:135-136).
+// time0, time1: the camera's shutter (camera.h:15-16) in place of the scene's
+// own, as a camera constructed with those t0, t1 has it.
 // bvh: the world's objects are put under one bvh_node (the host BVH); its
 // records must equal the flat hittable_list's.
 #include <cstdint>
@@ -64,8 +66,9 @@ struct render_type_access : scene {
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc != 9) {
-        std::fprintf(stderr, "usage: host_render <scene> <nx> <ny> <spp> <depth> <seed> <flat|bvh> <out.bin>\n");
+    if (argc != 9 && argc != 11) {
+        std::fprintf(stderr, "usage: host_render <scene> <nx> <ny> <spp> <depth> <seed> <flat|bvh> <out.bin> "
+                             "[<time0> <time1>]\n");
         return 2;
     }
     std::string name = argv[1];
@@ -81,6 +84,10 @@ int main(int argc, char** argv) {
     }
     if (normal) render_type_access::set(*sc, RenderType::Normal);
     camera& cam = sc->GetCamera();
+    if (argc == 11) {
+        cam.time0 = std::strtod(argv[9], nullptr);
+        cam.time1 = std::strtod(argv[10], nullptr);
+    }
     std::shared_ptr<hittable> tree;
     if (bvh) tree = std::make_shared<bvh_node>(sc->GetWorld().objects, cam.time0, cam.time1);
     const hittable& world = bvh ? *tree : static_cast<const hittable&>(sc->GetWorld());

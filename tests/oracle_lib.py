@@ -64,6 +64,18 @@ def oracle_sums(scene_desc, nx, ny, spp, max_depth, seed=0, threads=0, rows=None
     return out, seg.value
 
 
+def case_camera(scene_desc, case):
+    """The camera of a tests/golden/renders.json case: the scene's own (None),
+    or, where the case has "shutter": [t0, t1], a copy with time0/time1
+    overridden, as the reference's camera was constructed for that render."""
+    if "shutter" not in case:
+        return None
+    from raytracingweekend_amd import _abi
+    cam = _abi.rtw_camera_desc.from_buffer_copy(scene_desc.camera)
+    cam.time0, cam.time1 = case["shutter"]
+    return cam
+
+
 def ref_available() -> bool:
     return REF_BIN.exists()
 

@@ -10,6 +10,7 @@ glibc's in the last ulp; both perturb only the low bits of a path.
 import numpy as np
 import pytest
 
+from execution_forms import execution_forms_agree
 from oracle_lib import finalize_np, oracle_sums
 from raytracingweekend_amd import _abi
 
@@ -146,37 +147,6 @@ def test_reference_default_config_matches_committed_render(gpu):
     assert rms < 2.5, rms
 
 
-def _execution_forms_agree(gpu, monkeypatch, scene, bvh, normal=False):
-    nx, ny, spp, depth = 40, 30, 4, 50
-    sd = gpu.SceneDesc(scene, nx / ny, use_bvh=bvh)
-    if normal:
-        sd.desc.render_type = _abi.RTW_RENDER_NORMAL
-    ds = gpu.DeviceScene(sd)
-    try:
-        a, sa = ds.render_accumulate(nx, ny, spp, depth, seed=5)
-        kernels = [ds.query()["kernel"]]
-        monkeypatch.setenv("RTW_MODE", "wavefront")
-        b, sb = ds.render_accumulate(nx, ny, spp, depth, seed=5)
-        kernels.append(ds.query()["kernel"])
-        monkeypatch.setenv("RTW_SPLIT", "1")
-        c, sc = ds.render_accumulate(nx, ny, spp, depth, seed=5)
-        kernels.append(ds.query()["kernel"])
-    finally:
-        ds.close()
-    print(f"KERNELS forms {scene} bvh={bvh} normal={normal}: {kernels}")
-    assert kernels[0].startswith("k_persist") and kernels[1].startswith(("k_segment<", "k_intersect<"))
-    assert kernels[2].startswith("k_intersect<")
-    assert sa["segments"] == sb["segments"] == sc["segments"]
-    if normal:
-        assert sa["segments"] == nx * ny * spp
-    assert np.array_equal(a, b) and np.array_equal(a, c)
-    for sort in ("0", "1"):
-        d, sd_ = _render_in_child({"RTW_SORT": sort}, scene, nx, ny, spp, depth, 5, bvh, normal)
-        assert np.array_equal(a, d), f"RTW_SORT={sort}"
-        assert sd_ == sa["segments"], f"RTW_SORT={sort}"
-    return kernels
-
-
 @pytest.mark.parametrize("scene,bvh", [("cornell_box", False), ("random_balls", True), ("dielectric", False),
                                        ("nested", False)])
 def test_execution_forms_agree(gpu, monkeypatch, scene, bvh):
@@ -186,7 +156,7 @@ def test_execution_forms_agree(gpu, monkeypatch, scene, bvh):
     (k_segment; RTW_MODE=wavefront) and its split pair (k_intersect, k_shade;
     + RTW_SPLIT=1) run the same arithmetic in the same order per sample:
     bit-identical accumulators and segment counts."""
-    _execution_forms_agree(gpu, monkeypatch, scene, bvh)
+    execution_forms_agree(gpu, monkeypatch, scene, bvh)
 
 
 @pytest.mark.parametrize("scene,bvh", [("cornell_box", False), ("grouped_world", True)])
@@ -196,32 +166,9 @@ def test_execution_forms_agree_in_normal_mode(gpu, monkeypatch, scene, bvh):
     facts (`black`), so Cornell takes other instantiations here than in
     Shaded mode; grouped_world walks group BVHs under a world BVH in every
     form (the split pair's k_intersect<F_WBVH | F_GBVH> included)."""
-    kernels = _execution_forms_agree(gpu, monkeypatch, scene, bvh, normal=True)
+    kernels = execution_forms_agree(gpu, monkeypatch, scene, bvh, normal=True)
     if scene == "grouped_world":
         assert kernels[2] == "k_intersect<6>"  # F_WBVH | F_GBVH
-
-
-def _render_in_child(env, scene, nx, ny, spp, depth, seed, bvh, normal=False):
-    """Render in a fresh process with extra environment (for switches the
-    library reads once per process).  Returns (accumulator, segments)."""
-    import os
-    import subprocess
-    import sys
-    import tempfile
-    from pathlib import Path
-    root = Path(__file__).resolve().parents[1]
-    with tempfile.TemporaryDirectory() as td:
-        out = Path(td) / "acc.npy"
-        code = (f"import sys; sys.path.insert(0, {str(root)!r}); import numpy as np; "
-                f"from raytracingweekend_amd import render as r, _abi; "
-                f"sd = r.SceneDesc({scene!r}, {nx}/{ny}, use_bvh={bvh}); "
-                f"sd.desc.render_type = _abi.RTW_RENDER_NORMAL if {normal} else sd.desc.render_type; "
-                f"ds = r.DeviceScene(sd); "
-                f"a, st = ds.render_accumulate({nx}, {ny}, {spp}, {depth}, seed={seed}); ds.close(); "
-                f"np.save({str(out)!r}, a); print('SEGMENTS', st['segments'])")
-        r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, check=True, timeout=300,
-                           capture_output=True, text=True)
-        return np.load(out), int(r.stdout.split("SEGMENTS")[-1].split()[0])
 
 
 def test_device_finalize_matches_host(gpu):

@@ -39,6 +39,13 @@ CASES = [
     ("book2_final", 24, 24, 2, 50, True),
     ("nested", 24, 24, 4, 50, False),
 ]
+# the probe scenes (one shading feature each; tied to the reference's classes
+# by tests/golden/render_probe_*.npy): flat for all, and with BVHs where the
+# walk meets media, movers or the default-pdf light
+PROBE_KINDS = ["rect_light", "sphere_light", "far_sphere_light", "default_light", "glass", "metal", "medium",
+               "motion", "textures"]
+CASES += [(f"probe_{kind}", 32, 24, 4, 50, False) for kind in PROBE_KINDS]
+CASES += [(f"probe_{kind}", 32, 24, 4, 50, True) for kind in ("medium", "motion", "default_light")]
 
 
 @pytest.fixture(scope="module")

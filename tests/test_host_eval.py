@@ -18,6 +18,8 @@ ROOT = Path(__file__).resolve().parents[1]
 PKG = ROOT / "raytracingweekend_amd"
 GOLD = ROOT / "tests" / "golden"
 CASES = json.loads((GOLD / "renders.json").read_text())
+PROBE_KINDS = ["rect_light", "sphere_light", "far_sphere_light", "default_light", "glass", "metal", "medium",
+               "motion", "textures"]
 
 
 @pytest.fixture(scope="module")
@@ -31,10 +33,11 @@ def host_render(built, tmp_path_factory):
     return exe
 
 
-def render(exe, tmp_path, scene, nx, ny, spp, depth, seed, bvh=False):
+def render(exe, tmp_path, scene, nx, ny, spp, depth, seed, bvh=False, shutter=None):
     out = tmp_path / f"{scene.replace(':', '_')}_{'bvh' if bvh else 'flat'}.bin"
     r = subprocess.run([str(exe), scene, str(nx), str(ny), str(spp), str(depth), str(seed),
-                        "bvh" if bvh else "flat", str(out)], capture_output=True, text=True, timeout=300)
+                        "bvh" if bvh else "flat", str(out), *([repr(float(t)) for t in shutter] if shutter else [])],
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     sums = np.frombuffer(raw[:-8], dtype=np.float64)
@@ -48,7 +51,7 @@ def test_host_color_matches_reference_render(host_render, tmp_path, case):
     if case.get("render_type", "shaded") != "shaded":  # host_render's "normal:<scene>"
         scene = f"{case['render_type']}:{scene}"
     sums, seg = render(host_render, tmp_path, scene, case["nx"], case["ny"], case["spp"],
-                       case["max_depth"], case["seed"])
+                       case["max_depth"], case["seed"], shutter=case.get("shutter"))
     gold = np.load(GOLD / f"render_{case['case']}.npy")
     assert seg == case["segments"], "world traversals differ from the reference's"
     assert np.array_equal(sums, gold), f"max diff {np.abs(sums - gold).max()}"
@@ -58,7 +61,8 @@ def test_host_color_matches_reference_render(host_render, tmp_path, case):
                                              ("nested_plain", 24, 24, 2), ("dielectric", 32, 16, 2),
                                              ("light_sample", 32, 16, 2), ("book2_final", 16, 16, 2),
                                              ("nested", 24, 24, 2), ("grouped", 32, 24, 2),
-                                             ("grouped_world", 32, 24, 2), ("normal:grouped_world", 32, 24, 2)])
+                                             ("grouped_world", 32, 24, 2), ("normal:grouped_world", 32, 24, 2),
+                                             *[(f"probe_{kind}", 32, 24, 2) for kind in PROBE_KINDS]])
 def test_host_bvh_equals_flat_list(host_render, tmp_path, scene, nx, ny, spp):
     """bvh_node::hit (median-split tree, nearest-first walk, then the list
     walk over the objects reaching the closest distance) picks the same

@@ -13,7 +13,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from oracle_lib import finalize_np, oracle, oracle_sums
+from oracle_lib import case_camera, finalize_np, oracle, oracle_sums
 from raytracingweekend_amd import _abi
 
 GOLD = Path(__file__).resolve().parent / "golden"
@@ -31,7 +31,8 @@ def test_oracle_matches_reference_render(api, case):
     sd = api.SceneDesc(case["scene"], case["nx"] / case["ny"])
     if case.get("render_type", "shaded") == "normal":  # the reference's RenderType::Normal
         sd.desc.render_type = _abi.RTW_RENDER_NORMAL
-    sums, seg = oracle_sums(sd, case["nx"], case["ny"], case["spp"], case["max_depth"], seed=case["seed"])
+    sums, seg = oracle_sums(sd, case["nx"], case["ny"], case["spp"], case["max_depth"], seed=case["seed"],
+                            camera=case_camera(sd, case))
     gold = np.load(GOLD / f"render_{case['case']}.npy")
     assert seg == case["segments"]
     assert np.array_equal(sums, gold), f"max diff {np.abs(sums - gold).max()}"
