@@ -158,6 +158,42 @@ NOISE_SIGNATURES = {
                                             C.c_double, C.c_void_p, C.POINTER(rtw_noise_summary)]),
 }
 
+
+class rtw_adaptive_params(C.Structure):
+    """include/rtw_adaptive.h"""
+    _fields_ = [("target_rel", C.c_double), ("floor", C.c_double), ("min_spp", C.c_int32), ("max_spp", C.c_int32),
+                ("batch", C.c_int32), ("pad", C.c_int32)]
+
+
+class rtw_adaptive_result(C.Structure):
+    """include/rtw_adaptive.h"""
+    _fields_ = [("samples", C.c_uint64), ("pixels_at_max", C.c_uint64), ("rounds", C.c_uint32), ("pad", C.c_uint32),
+                ("final", rtw_noise_summary)]
+
+
+# the functions of include/rtw_adaptive.h (its own header, its own table)
+ADAPTIVE_SIGNATURES = {
+    "rtw_render_accumulate_active": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera_desc), C.POINTER(rtw_render_params),
+                                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(rtw_stats)]),
+    "rtw_adaptive_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                      C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rtw_adaptive_select_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rtw_noise_estimate_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                            C.c_void_p, C.POINTER(rtw_noise_summary)]),
+    "rtw_noise_estimate_counts_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                   C.c_double, C.c_void_p, C.POINTER(rtw_noise_summary)]),
+    "rtw_finalize_canvas_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "rtw_finalize_canvas_counts_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "rtw_adaptive_next_round": (C.c_int, [C.POINTER(rtw_adaptive_params), C.c_int, C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int)]),
+    "rtw_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera_desc), C.POINTER(rtw_render_params),
+                                      C.POINTER(rtw_adaptive_params), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(rtw_adaptive_result), C.POINTER(rtw_stats)]),
+    "rtw_scene_query_active": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p]),
+}
+
 _lib = None
 
 
@@ -178,7 +214,7 @@ def load_library(path) -> C.CDLL:
         raise RuntimeError(f"native library {path} is missing: build it with "
                            f"`python -m raytracingweekend_amd.build` (there is no CPU fallback)")
     L = C.CDLL(str(path))
-    for name, (res, args) in [*SIGNATURES.items(), *NOISE_SIGNATURES.items()]:
+    for name, (res, args) in [*SIGNATURES.items(), *NOISE_SIGNATURES.items(), *ADAPTIVE_SIGNATURES.items()]:
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

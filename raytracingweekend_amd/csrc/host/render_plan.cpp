@@ -15,8 +15,10 @@ int rtw_check_sample_range(const rtw_render_params& R, const char* entry, const 
 }
 
 int rtw_plan_call(const rtw_render_params& R, const rtw_camera_desc& camera, const layout_facts& facts,
-                  const void* accum_rgb, const void* accum_sq, size_t budget, int flog_cus, call_plan* out) {
+                  const void* accum_rgb, const void* accum_sq, size_t budget, int flog_cus, call_plan* out,
+                  const call_active* act) {
     call_plan P;
+    P.active = act != nullptr;
     if (int rc = rtw_check_sample_range(R, "rtw_render_accumulate", "", &P.spp_count)) return rc;
     if (R.precision != RTW_PRECISION_FP64 && R.precision != RTW_PRECISION_FP32)
         return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate: unknown precision");
@@ -26,6 +28,16 @@ int rtw_plan_call(const rtw_render_params& R, const rtw_camera_desc& camera, con
     P.npix = (uint64_t)P.n_rows * (uint64_t)R.nx;
     if ((uint64_t)R.nx * R.ny >= (1ull << 32) || P.npix >= (1ull << 31))
         return rtw_fail(RTW_ERR_INVALID, "image too large for 32-bit pixel ids");
+    if (act) {
+        // the list replaces row sharding: sample ids index it
+        if (R.row_begin != 0 || R.row_step > 1)
+            return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_active: row_begin / row_step do not apply to a "
+                                             "pixel list (row_begin 0, row_step 0 or 1)");
+        if (act->n > P.npix)
+            return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_active: more active pixels than the image has");
+        if (act->n && !act->list) return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_active: null pixel list");
+        P.npix = act->n;
+    }
     if (facts.bvh_motion && (std::min(camera.time0, camera.time1) < facts.shutter0 ||
                              std::max(camera.time0, camera.time1) > facts.shutter1))
         return rtw_fail(RTW_ERR_INVALID,
@@ -34,8 +46,22 @@ int rtw_plan_call(const rtw_render_params& R, const rtw_camera_desc& camera, con
     const size_t img_bytes = (size_t)R.nx * R.ny * 24;
     if (accum_sq && rtw_ranges_overlap(accum_rgb, accum_sq, img_bytes))
         return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_moments: accum_rgb and accum_sq_rgb overlap");
+    if (act) {
+        // (a duplicate in the list or a buffer under another would make the
+        // scatter-add a race)
+        const struct {
+            const void* p;
+            size_t bytes;
+        } buf[] = {{accum_rgb, img_bytes}, {accum_sq, img_bytes}, {act->counts, img_bytes / 6}, {act->list, act->n * 4}};
+        for (int a = 0; a < 4; ++a)
+            for (int b = a + 1; b < 4; ++b)
+                if (buf[a].p && buf[b].p && buf[a].bytes && buf[b].bytes &&
+                    rtw_spans_overlap(buf[a].p, buf[a].bytes, buf[b].p, buf[b].bytes))
+                    return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_active: two of accum_rgb, accum_sq_rgb, "
+                                                     "counts and the pixel list overlap");
+    }
 
-    if (P.spp_count == 0 || R.max_depth <= 0) {
+    if (P.spp_count == 0 || R.max_depth <= 0 || P.npix == 0) {
         // color() with depth <= 0 returns 0 (RayTracingWeekend.cpp:47-48):
         // every sample adds zero radiance, the accumulator is unchanged.
         P.noop = true;
@@ -65,6 +91,10 @@ int rtw_plan_call(const rtw_render_params& R, const rtw_camera_desc& camera, con
     P.bytes.run2 = accum_sq ? P.npix * 24 : 0;
     P.bytes.camera = sizeof(rtw_camera_desc) + 2 * sizeof(double);
     P.bytes.staging = R.accum_on_device ? 0 : img_bytes;
+    if (act && !R.accum_on_device) {
+        P.bytes.list = P.npix * 4;
+        P.bytes.counts = act->counts ? img_bytes / 6 : 0;
+    }
 
     // camera_sample<false>'s pinhole test reads lens_radius and the origin; a
     // lens-less camera whose u or v is not finite gets lens_radius NaN in the

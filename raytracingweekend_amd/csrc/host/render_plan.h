@@ -29,13 +29,25 @@ struct call_bytes {
     size_t camera = 0;    // the device camera and k_recips' two reciprocals after it
     size_t flog = 0;      // the strict build's factor logs
     size_t staging = 0;   // a whole image: the device copy of a host accumulator (each of the two)
+    size_t list = 0;      // an active call: the device copy of a host pixel list
+    size_t counts = 0;    // ... and of a host counts buffer (a whole image of uint32)
+};
+
+// The pixel list of rtw_render_accumulate_active (rtw_adaptive.h), as far as
+// the plan reads it: its length and, for the overlap checks only, where the
+// list and the counts lie.
+struct call_active {
+    uint64_t n = 0;
+    const void* list = nullptr;
+    const void* counts = nullptr;  // may be null
 };
 
 struct call_plan {
     // the resolved call
     int spp_count = 0, row_step = 1, n_rows = 0;
-    uint64_t npix = 0;      // n_rows * nx
-    bool noop = false;      // no samples or max_depth <= 0: the accumulator is unchanged, nothing is sized
+    uint64_t npix = 0;      // n_rows * nx; an active call: the list's length
+    bool active = false;    // an active call (sample ids index the list: job_t's rows are not read)
+    bool noop = false;     // no samples or max_depth <= 0: the accumulator is unchanged, nothing is sized
     uint64_t samples = 0;   // stats.samples of a no-op (spp_count * npix: every sample adds zero)
     bool fast = false;      // precision fp32
     uint32_t pool = 0;      // paths in flight (wavefront form)
@@ -74,8 +86,15 @@ int rtw_check_sample_range(const rtw_render_params& R, const char* entry, const 
 // may hold (RTW_PASS_SAMPLES).  flog_cus: the device's CUs in the strict
 // build, else 0.  RTW_OK, or RTW_ERR_INVALID with the reason; after the
 // refusals nothing in it fails.
+// act (null: a whole-image call, planned as ever): the call renders the
+// act->n listed pixels.  The list takes the rows' place: npix, the passes,
+// div_npix and the per-pixel buffers are sized by act->n, `list` and `counts`
+// are the device copies a host call needs.  Refused: row_begin != 0 or
+// row_step > 1, a null list, more pixels than the image has, and any two of
+// the four buffers overlapping.  An empty list is a no-op of 0 samples.
 int rtw_plan_call(const rtw_render_params& R, const rtw_camera_desc& camera, const layout_facts& facts,
-                  const void* accum_rgb, const void* accum_sq, size_t budget, int flog_cus, call_plan* out);
+                  const void* accum_rgb, const void* accum_sq, size_t budget, int flog_cus, call_plan* out,
+                  const call_active* act = nullptr);
 
 call_pass rtw_plan_pass(const call_plan& P, const rtw_render_params& R, uint64_t done);
 

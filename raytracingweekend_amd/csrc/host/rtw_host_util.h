@@ -40,6 +40,11 @@ int rtw_check_device_ptr(const void* p, int device, const char* what, bool allow
 // the argument checks of rtw_noise_estimate[_device], whether two buffers of
 // `bytes` bytes share a byte, and the summary from the image-wide sums.
 bool rtw_ranges_overlap(const void* a, const void* b, size_t bytes);
+// ... and of two buffers of different sizes: [a, a+na) and [b, b+nb) share a byte
+inline bool rtw_spans_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y ? y - x < na : x - y < nb;
+}
 int rtw_noise_check_args(const char* what, const void* accum, const void* accum_sq, int nx, int ny, int n,
                          double floor, const void* stderr_rgb);
 void rtw_noise_finish(uint64_t pixels, uint64_t nonfinite, double sum_rel, double max_rel, double sum_se2,

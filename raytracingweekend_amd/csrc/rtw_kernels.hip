@@ -42,6 +42,7 @@
 #include "rtw_device.h"
 #include "rtw_fast.h"
 #include "rtw_queue.h"
+#include "host/adaptive.h"
 #include "host/render_plan.h"
 #include "host/rtw_host_util.h"
 #include "host/scene_layout.h"
@@ -105,14 +106,38 @@ __device__ __forceinline__ void store_record(T* o, T x, T y, T z) {
     o[0] = x, o[1] = y, o[2] = z;
 }
 
+// An active call (rtw_adaptive.h) has no row sharding: its pixel list lies
+// over row_begin / row_step, 8 bytes at an 8-byte-aligned offset.  job_t is
+// the middle of the persistent kernels' argument and its layout theirs, so it
+// does not grow; only kernels compiled with F_ACTIVE read the pointer.
+static_assert(offsetof(job_t, row_begin) % 8 == 0 && offsetof(job_t, row_step) == offsetof(job_t, row_begin) + 4,
+              "the active list's pointer overlays row_begin / row_step");
+__device__ __forceinline__ const uint32_t* job_active_list(const job_t& J) {
+    const uint32_t* list;
+    __builtin_memcpy(&list, &J.row_begin, sizeof list);
+    return list;
+}
+
 // pass-local sample id -> pixel (i, j) and global sample index s
+// ACTIVE: the id's pixel part indexes the call's list of pixel indices (one
+// coalesced 4-byte load per new camera sample, in the refill phase; not
+// loop-carried).  Ids stay dense in [0, spp_pass * n_active), so the RNG key
+// j*nx + i, the jitter and the record at L[3q] need nothing else.
+template <bool ACTIVE = false>
 __device__ __forceinline__ void sample_coords(const job_t& J, uint32_t q, int& i, int& j, int& s) {
 // (the quotients by exact magic-number division, rtw_div.h udiv_fast)
     const uint32_t sl = udiv_fast(q, J.div_npix);
     const uint32_t rem = q - sl * J.npix;
-    const uint32_t k = udiv_fast(rem, J.div_nx);
-    i = (int)(rem - k * (uint32_t)J.nx);
-    j = J.row_begin + (int)k * J.row_step;
+    if constexpr (ACTIVE) {
+        const uint32_t pixel = job_active_list(J)[rem];
+        const uint32_t k = udiv_fast(pixel, J.div_nx);
+        i = (int)(pixel - k * (uint32_t)J.nx);
+        j = (int)k;
+    } else {
+        const uint32_t k = udiv_fast(rem, J.div_nx);
+        i = (int)(rem - k * (uint32_t)J.nx);
+        j = J.row_begin + (int)k * J.row_step;
+    }
     s = J.s_begin + (int)sl;
 }
 
@@ -125,10 +150,10 @@ __device__ __forceinline__ void sample_coords(const job_t& J, uint32_t q, int& i
 // measure differently through code layout alone: J.cam_pin T +0.6 %, the
 // camera test C3 +1.5 %, profiles/r06/ab_r6h_*.log; each kernel takes its
 // better one.)
-template <bool JPIN = true>
+template <bool JPIN = true, bool ACTIVE = false>
 __device__ __forceinline__ ray camera_sample(const job_t& J, uint32_t q, uint32_t& rng) {
     int i, j, s;
-    sample_coords(J, q, i, j, s);
+    sample_coords<ACTIVE>(J, q, i, j, s);
     rng = path_seed(J.seed_mix, (uint32_t)(j * J.nx + i), (uint32_t)s);
     // The camera (23 doubles) is loaded here, with scalar loads, each time
     // rays are made: an opaque pointer stops the compiler from hoisting it
@@ -167,19 +192,21 @@ __device__ __forceinline__ ray camera_sample(const job_t& J, uint32_t q, uint32_
 }
 // ... and of the fp32 fast mode (rtw_fast.h): the same sample decomposition
 // and engine, single-precision jitter and camera
+template <bool ACTIVE = false>
 __device__ __forceinline__ rtwf::fray camera_sample_f32(const job_t& J, const rtwf::cam32& cam, uint32_t q,
                                                         uint32_t& rng) {
     int i, j, s;
-    sample_coords(J, q, i, j, s);
+    sample_coords<ACTIVE>(J, q, i, j, s);
     rng = path_seed(J.seed_mix, (uint32_t)(j * J.nx + i), (uint32_t)s);
     const float u = ((float)i + rtwf::u01(rng)) * rtwf::rcp((float)J.nx);
     const float v = ((float)j + rtwf::u01(rng)) * rtwf::rcp((float)J.ny);
     return rtwf::camera_ray(cam, u, v, rng);
 }
 
+template <bool ACTIVE = false>
 __device__ __forceinline__ void raygen(const job_t& J, const fresh_t& F, uint32_t k, uint32_t q) {
     uint32_t rng;
-    const ray r = camera_sample(J, q, rng);
+    const ray r = camera_sample<true, ACTIVE>(J, q, rng);
     F.ox[k] = r.o.x, F.oy[k] = r.o.y, F.oz[k] = r.o.z;
     F.dx[k] = r.d.x, F.dy[k] = r.d.y, F.dz[k] = r.d.z;
     F.tm[k] = r.t;
@@ -909,7 +936,7 @@ void k_persist(persist_args) {
                     if (left) open = false;
                     if (got) {  // (lanes >= NB get no id)
                         uint32_t rng;
-                        const ray r = camera_sample<false>(J, q, rng);
+                        const ray r = camera_sample<false, (F & F_ACTIVE) != 0>(J, q, rng);
                         if constexpr (!PIN) B.ox[ln] = r.o.x, B.oy[ln] = r.o.y, B.oz[ln] = r.o.z;
                         B.dx[ln] = r.d.x, B.dy[ln] = r.d.y, B.dz[ln] = r.d.z;
                         B.tm[ln] = r.t;
@@ -1222,7 +1249,7 @@ void k_persist_sort(persist_args) {
                 }
                 if (left) open = false;
                 if (got) {
-                    const ray r = camera_sample(J, q, x.rng);
+                    const ray r = camera_sample<true, (F & F_ACTIVE) != 0>(J, q, x.rng);
                     const uint32_t me = threadIdx.x;
                     const uint32_t home = X.home[me];
                     X.put_ray(me, r);
@@ -1395,7 +1422,7 @@ void k_fast(fast_args) {
             const reservation rs = reserve_samples(A.C, A.J.total, m, idle);
             open = rs.open;
             if (rs.got) {
-                r = camera_sample_f32(A.J, A.cam, rs.q, rng);
+                r = camera_sample_f32<(F & F_ACTIVE) != 0>(A.J, A.cam, rs.q, rng);
                 thr = f3{1, 1, 1};
                 q = rs.q;
                 depth = (uint32_t)A.J.max_depth;
@@ -1497,7 +1524,7 @@ void k_fast_sort(fast_args, const char* base, uint32_t bytes) {
                 const uint32_t q = rs.q;
                 open = rs.open;
                 if (rs.got) {
-                    const fray r = camera_sample_f32(A.J, A.cam, q, rng);
+                    const fray r = camera_sample_f32<(F & F_ACTIVE) != 0>(A.J, A.cam, q, rng);
                     X.put_ray(me, r);
                     X.q[me] = q;
                     depth = (uint32_t)A.J.max_depth;
@@ -1581,7 +1608,8 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* s_wave, uin
 // measured 52 us vs 5 us per launch for 13 scattered arrays vs 3.)
 constexpr uint32_t kRegenSlots = 1024;
 
-__global__ __launch_bounds__(kBlock) void k_regen(job_t J, paths_t P, fresh_t FR, ctrs_t* C) {
+template <bool ACTIVE>
+__device__ __forceinline__ void regen_block(const job_t& J, const paths_t& P, const fresh_t& FR, ctrs_t* C) {
     __shared__ uint32_t s_wave[kWaves];
     __shared__ uint32_t s_list[kRegenSlots];
     const uint32_t n = C->n;
@@ -1634,13 +1662,22 @@ __global__ __launch_bounds__(kBlock) void k_regen(job_t J, paths_t P, fresh_t FR
         for (int a = 0; a < kQShards; ++a) {
             if (k < s_got[a]) {
                 const int sh = (own + a) % kQShards;
-                raygen(J, FR, lo + e, (uint32_t)shard_sample(sh, s_first[a] + k));
+                raygen<ACTIVE>(J, FR, lo + e, (uint32_t)shard_sample(sh, s_first[a] + k));
                 P.depth[s_list[e]] = kFresh | (lo + e);
                 break;
             }
             k -= s_got[a];
         }
     }
+}
+__global__ __launch_bounds__(kBlock) void k_regen(job_t J, paths_t P, fresh_t FR, ctrs_t* C) {
+    regen_block<false>(J, P, FR, C);
+}
+// ... of an active call (rtw_adaptive.h): the only wavefront kernel that makes
+// camera rays, so this one instantiation serves every feature and material set
+// with the unchanged k_segment / k_intersect / k_shade
+__global__ __launch_bounds__(kBlock) void k_regen_active(job_t J, paths_t P, fresh_t FR, ctrs_t* C) {
+    regen_block<true>(J, P, FR, C);
 }
 
 // Tail-phase stream compaction of live slots (depth != 0) from A into B
@@ -1748,11 +1785,62 @@ __global__ __launch_bounds__(kBlock) void k_emit(const double* __restrict__ run,
     }
 }
 
+// An active call's scatter-add (rtw_adaptive.h): accum[active[k]] += run[k],
+// the same for the sums of squares, counts[active[k]] += spp (each of the
+// three where its pointer is set).  The list is strictly ascending
+// (k_check_active), so no two threads write one pixel.
+__global__ __launch_bounds__(kBlock) void k_emit_active(const double* __restrict__ run, const double* __restrict__ run2,
+                                                        uint32_t n, const uint32_t* __restrict__ active, uint32_t spp,
+                                                        double* __restrict__ accum, double* __restrict__ accum_sq,
+                                                        uint32_t* __restrict__ counts) {
+    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < n; k += gridDim.x * kBlock) {
+        const uint32_t p = active[k];
+        const size_t o = (size_t)p * 3;
+        if (run) {
+            accum[o] += run[3 * k];
+            accum[o + 1] += run[3 * k + 1];
+            accum[o + 2] += run[3 * k + 2];
+        }
+        if (run2) {
+            accum_sq[o] += run2[3 * k];
+            accum_sq[o + 1] += run2[3 * k + 1];
+            accum_sq[o + 2] += run2[3 * k + 2];
+        }
+        if (counts) counts[p] += spp;
+    }
+}
+
+// *bad = 1 unless active[0..n) is strictly ascending and below `limit` (the
+// image's pixel count); *bad is zero before the launch.  Every thread that
+// finds a fault stores the same 1.
+__global__ __launch_bounds__(kBlock) void k_check_active(const uint32_t* __restrict__ active, uint32_t n,
+                                                         uint32_t limit, uint32_t* __restrict__ bad) {
+    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < n; k += gridDim.x * kBlock) {
+        const uint32_t p = active[k];
+        if (p >= limit || (k > 0 && active[k - 1] >= p)) *bad = 1u;
+    }
+}
+
+// counts[p] = v for the whole image (the adaptive loop's round 0)
+__global__ __launch_bounds__(kBlock) void k_set_counts(uint32_t* __restrict__ counts, size_t n, uint32_t v) {
+    for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) counts[k] = v;
+}
+
 // canvas = min(sqrt(accum / spp), 1) (RayTracingWeekend.cpp:241-244)
 __global__ __launch_bounds__(kBlock) void k_finalize(const double* __restrict__ accum, size_t n, double spp,
                                                      double* __restrict__ canvas) {
     for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
         const double s = __builtin_sqrt(accum[k] / spp);
+        canvas[k] = (1.0 < s) ? 1.0 : s;
+    }
+}
+
+// ... with each pixel's own sample count (rtw_finalize_canvas_counts)
+__global__ __launch_bounds__(kBlock) void k_finalize_counts(const double* __restrict__ accum,
+                                                            const uint32_t* __restrict__ counts, size_t n,
+                                                            double* __restrict__ canvas) {
+    for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
+        const double s = __builtin_sqrt(accum[k] / (double)counts[k / 3]);
         canvas[k] = (1.0 < s) ? 1.0 : s;
     }
 }
@@ -1772,6 +1860,34 @@ struct noise_part {
 constexpr unsigned kNoiseMaxGrid = 1024;
 unsigned noise_grid(uint64_t npix) {
     return (unsigned)std::min<uint64_t>((npix + kBlock - 1) / kBlock, kNoiseMaxGrid);
+}
+
+// A block's partial of the summary from its threads' (k_noise_pixels' fold:
+// a fixed shuffle tree per wave, then thread 0 over the waves in wave order).
+// Every thread of the block calls it.
+__device__ __forceinline__ void noise_fold(noise_part a, noise_part* s_part, noise_part* __restrict__ parts) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a.sum_rel = a.sum_rel + __shfl_down(a.sum_rel, off, 64);
+        a.sum_se2 = a.sum_se2 + __shfl_down(a.sum_se2, off, 64);
+        const double mx = __shfl_down(a.max_rel, off, 64);
+        if (mx > a.max_rel) a.max_rel = mx;
+        a.pixels += __shfl_down(a.pixels, off, 64);
+        a.nonfinite += __shfl_down(a.nonfinite, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        noise_part t = s_part[0];
+        for (int w = 1; w < kWaves; ++w) {
+            t.sum_rel = t.sum_rel + s_part[w].sum_rel;
+            t.sum_se2 = t.sum_se2 + s_part[w].sum_se2;
+            if (s_part[w].max_rel > t.max_rel) t.max_rel = s_part[w].max_rel;
+            t.pixels += s_part[w].pixels;
+            t.nonfinite += s_part[w].nonfinite;
+        }
+        parts[blockIdx.x] = t;
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void k_noise_pixels(const double* __restrict__ accum,
@@ -1811,27 +1927,121 @@ __global__ __launch_bounds__(kBlock) void k_noise_pixels(const double* __restric
         a.sum_se2 = a.sum_se2 + ((se[0] * se[0] + se[1] * se[1]) + se[2] * se[2]);
     }
     // (all 256 threads reach here: the loop above has no barrier)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a.sum_rel = a.sum_rel + __shfl_down(a.sum_rel, off, 64);
-        a.sum_se2 = a.sum_se2 + __shfl_down(a.sum_se2, off, 64);
-        const double mx = __shfl_down(a.max_rel, off, 64);
-        if (mx > a.max_rel) a.max_rel = mx;
-        a.pixels += __shfl_down(a.pixels, off, 64);
-        a.nonfinite += __shfl_down(a.nonfinite, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        noise_part t = s_part[0];
-        for (int w = 1; w < kWaves; ++w) {
-            t.sum_rel = t.sum_rel + s_part[w].sum_rel;
-            t.sum_se2 = t.sum_se2 + s_part[w].sum_se2;
-            if (s_part[w].max_rel > t.max_rel) t.max_rel = s_part[w].max_rel;
-            t.pixels += s_part[w].pixels;
-            t.nonfinite += s_part[w].nonfinite;
+    noise_fold(a, s_part, parts);
+}
+
+// ... with each pixel's own sample count n = counts[p] (rtw_adaptive.h
+// rtw_noise_estimate_counts: adaptive.h's rtw_pixel_rel, the host's
+// function): the same grid, the same per-thread pixel order and the same fold
+// as k_noise_pixels, so uniform counts give its bits.  A pixel with fewer than
+// two samples is left out as a non-finite one is.
+__global__ __launch_bounds__(kBlock) void k_noise_pixels_counts(const double* __restrict__ accum,
+                                                                const double* __restrict__ accum_sq,
+                                                                const uint32_t* __restrict__ counts, uint64_t npix,
+                                                                double floor3, double* __restrict__ stderr_rgb,
+                                                                noise_part* __restrict__ parts) {
+    __shared__ noise_part s_part[kWaves];
+    noise_part a;
+    a.sum_rel = 0.0, a.max_rel = -__builtin_inf(), a.sum_se2 = 0.0, a.pixels = 0, a.nonfinite = 0;
+    for (uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x; p < npix; p += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t n = counts[p];
+        double se[3], rel = 0.0;
+        bool finite = false;
+        if (n >= 2) {
+            const double s1[3] = {accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]};
+            const double s2[3] = {accum_sq[3 * p], accum_sq[3 * p + 1], accum_sq[3 * p + 2]};
+            rel = rtw_pixel_rel(s1, s2, (double)n, (double)(n - 1), floor3, se, &finite);
         }
-        parts[blockIdx.x] = t;
+        if (!finite) {
+            ++a.nonfinite;
+            if (stderr_rgb) {
+                const double nan = __builtin_nan("");
+                stderr_rgb[3 * p] = nan, stderr_rgb[3 * p + 1] = nan, stderr_rgb[3 * p + 2] = nan;
+            }
+            continue;
+        }
+        if (stderr_rgb) stderr_rgb[3 * p] = se[0], stderr_rgb[3 * p + 1] = se[1], stderr_rgb[3 * p + 2] = se[2];
+        ++a.pixels;
+        a.sum_rel = a.sum_rel + rel;
+        if (rel > a.max_rel) a.max_rel = rel;
+        a.sum_se2 = a.sum_se2 + ((se[0] * se[0] + se[1] * se[1]) + se[2] * se[2]);
+    }
+    noise_fold(a, s_part, parts);
+}
+
+// rtw_adaptive_select_device: the ascending list of the active pixels
+// (adaptive.h rtw_pixel_active, the host's function) without atomics.  Block b
+// owns the pixels [b * chunk, (b + 1) * chunk), chunk a multiple of kBlock, and
+// walks them in tiles of kBlock: k_select_count leaves each block's number of
+// active pixels, k_select_scan their exclusive prefix (and the total after the
+// last), k_select_scatter walks the same tiles again and writes each active
+// pixel at its block's base plus its rank (block_rank: ballot / popcount).
+// The grid depends on the pixel count only (select_grid).
+constexpr unsigned kSelectMaxGrid = 1024;
+unsigned select_grid(uint64_t npix) {
+    return (unsigned)std::min<uint64_t>((npix + kBlock - 1) / kBlock, kSelectMaxGrid);
+}
+uint64_t select_chunk(uint64_t npix) {
+    const uint64_t g = select_grid(npix);
+    return ((npix + g - 1) / g + kBlock - 1) / kBlock * kBlock;
+}
+struct select_args {
+    const double *accum, *accum_sq;
+    const uint32_t* counts;
+    uint64_t npix, chunk;
+    double floor3, target_rel;
+    uint32_t max_count;
+};
+__device__ __forceinline__ bool select_flag(const select_args& A, uint64_t p) {
+    if (p >= A.npix) return false;
+    const double s1[3] = {A.accum[3 * p], A.accum[3 * p + 1], A.accum[3 * p + 2]};
+    const double s2[3] = {A.accum_sq[3 * p], A.accum_sq[3 * p + 1], A.accum_sq[3 * p + 2]};
+    return rtw_pixel_active(s1, s2, A.counts[p], A.floor3, A.target_rel, A.max_count);
+}
+__global__ __launch_bounds__(kBlock) void k_select_count(select_args A, uint32_t* __restrict__ block_counts) {
+    __shared__ uint32_t s_wave[kWaves];
+    const uint64_t lo = blockIdx.x * A.chunk;
+    uint32_t mine = 0;
+    for (uint64_t t = 0; t < A.chunk; t += kBlock) mine += select_flag(A, lo + t + threadIdx.x) ? 1u : 0u;
+    uint32_t total;
+    block_scan(mine, s_wave, total);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+}
+// one block: offsets[b] = block_counts[0] + ... + block_counts[b - 1], offsets[n_blocks] = the total
+__global__ __launch_bounds__(kBlock) void k_select_scan(const uint32_t* __restrict__ block_counts, uint32_t n_blocks,
+                                                        uint32_t* __restrict__ offsets) {
+    __shared__ uint32_t s_wave[kWaves];
+    constexpr uint32_t kPer = kSelectMaxGrid / kBlock;
+    uint32_t v[kPer], mine = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kPer; ++k) {
+        const uint32_t b = threadIdx.x * kPer + k;
+        v[k] = b < n_blocks ? block_counts[b] : 0u;
+        mine += v[k];
+    }
+    uint32_t total;
+    uint32_t off = block_scan(mine, s_wave, total);
+#pragma unroll
+    for (uint32_t k = 0; k < kPer; ++k) {
+        const uint32_t b = threadIdx.x * kPer + k;
+        if (b < n_blocks) offsets[b] = off;
+        off += v[k];
+    }
+    if (threadIdx.x == 0) offsets[n_blocks] = total;
+}
+__global__ __launch_bounds__(kBlock) void k_select_scatter(select_args A, const uint32_t* __restrict__ offsets,
+                                                           uint32_t* __restrict__ active) {
+    __shared__ uint32_t s_wave[kWaves];
+    const uint64_t lo = blockIdx.x * A.chunk;
+    uint32_t base = offsets[blockIdx.x];
+    for (uint64_t t = 0; t < A.chunk; t += kBlock) {
+        const uint64_t p = lo + t + threadIdx.x;
+        const bool on = select_flag(A, p);
+        uint32_t total;
+        const uint32_t rank = block_rank(on, s_wave, total);
+        if (on) active[base + rank] = (uint32_t)p;
+        base += total;
+        __syncthreads();  // (s_wave is rewritten by the next tile)
     }
 }
 
@@ -1887,6 +2097,10 @@ struct handle_t {
     dev_buf run2;     // rtw_render_accumulate_moments: per-pixel running sums of squares
     dev_buf accum_sq; // ... device accum_sq when the caller passes a host pointer
     dev_buf noise;    // rtw_noise_estimate_device: per-block partials (noise_part)
+    // rtw_adaptive.h
+    dev_buf alist;    // the device copy of a host pixel list; the adaptive loop's list
+    dev_buf counts;   // the device copy of a host counts buffer; the adaptive loop's counts
+    dev_buf sel;      // rtw_adaptive_select_device: per-block counts, their prefix, the list check's flag
     dev_buf ctrs;
     dev_buf camera;                // device copy of the call's camera
     rtw_camera_desc cam_host{};    // its source (lives until the copy ran)
@@ -2069,6 +2283,30 @@ template <size_t... I>
 std::array<const void*, sizeof...(I)> intersect_rows(std::index_sequence<I...>) {
     return {reinterpret_cast<const void*>(&k_intersect<kIntersectList[I].f>)...};
 }
+// ... and the active lists' rows: one kernel each, in the row's form
+template <size_t I>
+const void* persist_active_fn() {
+    constexpr active_inst a = kPersistActiveList[I];
+    if constexpr (a.form == kform::persist_sort)
+        return reinterpret_cast<const void*>(&k_persist_sort<a.id.f, a.id.m, a.id.l>);
+    else
+        return reinterpret_cast<const void*>(&k_persist<a.id.f, a.id.m, a.id.l, a.form == kform::persist_lst>);
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> persist_active_rows(std::index_sequence<I...>) {
+    return {persist_active_fn<I>()...};
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> fast_active_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_fast<kFastActiveList[I].id.f, kFastActiveList[I].id.l>)...};
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> fast_sort_active_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_fast_sort<kFastSortActiveList[I].id.f, kFastSortActiveList[I].id.l>)...};
+}
+const auto kPersistActiveRows = persist_active_rows(std::make_index_sequence<kPersistActiveList.size()>{});
+const auto kFastActiveRows = fast_active_rows(std::make_index_sequence<kFastActiveList.size()>{});
+const auto kFastSortActiveRows = fast_sort_active_rows(std::make_index_sequence<kFastSortActiveList.size()>{});
 const auto kShadeRows = shade_rows(std::make_index_sequence<kShadeList.size()>{});
 const auto kIntersectRows = intersect_rows(std::make_index_sequence<kIntersectList.size()>{});
 const auto kPersistRows = persist_rows(std::make_index_sequence<kPersistList.size()>{});
@@ -2117,9 +2355,12 @@ struct plan_t {
     size_t shm = 0;            // LDS bytes of the scene's shading data (0: read through the caches)
     uint32_t packet = 0;       // BVH nodes staged in LDS (persist_lst, fast with LDS stacks)
 };
-int plan_render(const handle_t* h, bool pin, bool fast, plan_t* out) {
+// active: of a pixel list (select_active: a row of the active lists, or a
+// wavefront form, which wavefront_pass refills with k_regen_active).
+int plan_render(const handle_t* h, bool pin, bool fast, plan_t* out, bool active = false) {
     select_in s = scene_facts(h, pin);
     s.env = read_env();
+    s.active = active;
     plan_t p{fast ? select_fp32(s) : select_fp64(s)};
     const kform form = p.c.form;
     if (form == kform::split) {  // (its rows cover every choice: split_resolve)
@@ -2133,21 +2374,29 @@ int plan_render(const handle_t* h, bool pin, bool fast, plan_t* out) {
     const inst& id = p.c.id;
     p.shm = !id.l ? 0 : form == kform::fast_sort ? h->facts.f32_bytes : form == kform::fast ? 0 : h->facts.shade_bytes;
     const bool fp64 = form == kform::persist_sort || form == kform::persist || form == kform::persist_lst;
-    const int at = fp64 ? index_of(kPersistList, id) : form == kform::segment ? index_of(kSegmentList, id)
+    const bool act = active && form != kform::segment;  // (a row of the active lists)
+    const active_inst arow{id, form};
+    const int at = act ? (fp64 ? index_of(kPersistActiveList, arow)
+                          : form == kform::fast ? index_of(kFastActiveList, arow) : index_of(kFastSortActiveList, arow))
+                 : fp64 ? index_of(kPersistList, id) : form == kform::segment ? index_of(kSegmentList, id)
                  : form == kform::fast ? index_of(kFastList, id)
                  : form == kform::fast_sort ? index_of(kFastSortList, id) : 0;
     if (at < 0) return rtw_fail(RTW_ERR_HIP, "no such instantiation: " + p.c.name);
     if (fp64) {
-        const persist_row& r = kPersistRows[at];
-        p.fn = form == kform::persist_sort ? r.sort : form == kform::persist ? r.plain : r.lst;
+        if (act) {
+            p.fn = kPersistActiveRows[at];
+        } else {
+            const persist_row& r = kPersistRows[at];
+            p.fn = form == kform::persist_sort ? r.sort : form == kform::persist ? r.plain : r.lst;
+        }
         if (form == kform::persist_lst) p.packet = node_packet(p.fn, kPBlock, p.shm, h->S.n_nodes);
     } else if (form == kform::segment) {
         p.fn = kSegmentRows[at];
     } else if (form == kform::fast) {
-        p.fn = kFastRows[at];
+        p.fn = act ? kFastActiveRows[at] : kFastRows[at];
         if (id.l) p.packet = node_packet(p.fn, rtwf::fast_block(id.f), 0, h->F32.n_nodes);
     } else if (form == kform::fast_sort) {
-        p.fn = kFastSortRows[at];
+        p.fn = act ? kFastSortActiveRows[at] : kFastSortRows[at];
     }
     *out = p;
     return RTW_OK;
@@ -2440,8 +2689,13 @@ int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, const call_p
     const int check_every = 4;
     const uint32_t n0 = pass.fill;
     int rc;
+    // the refill: camera rays of the image's rows, or of the call's pixel list
+    const auto regen = [&] {
+        if (plan.c.active) hipLaunchKernelGGL(k_regen_active, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
+        else hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
+    };
     hipLaunchKernelGGL(k_fill, dim3((n0 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, W.A, C, n0);
-    hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
+    regen();
     HIPCHK(hipGetLastError());
     bool tail = false;
     std::vector<size_t> checks;  // event slots of status copies, with their copy index
@@ -2460,7 +2714,7 @@ int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, const call_p
             });
             if (rc) return rc;
         }
-        if (!tail) hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
+        if (!tail) regen();
         HIPCHK(hipGetLastError());
         stats.launches_intersect++;
         stats.iterations++;
@@ -2503,6 +2757,8 @@ int ensure_buffers(handle_t* h, const call_bytes& b, bool moments) {
     if ((rc = h->flog.ensure(b.flog))) return rc;
     if ((rc = h->accum.ensure(b.staging))) return rc;
     if (moments && (rc = h->accum_sq.ensure(b.staging))) return rc;
+    if ((rc = h->alist.ensure(b.list))) return rc;
+    if ((rc = h->counts.ensure(b.counts))) return rc;
     return RTW_OK;
 }
 
@@ -2524,6 +2780,10 @@ job_t make_job(const handle_t* h, const call_plan& P, const rtw_render_params& R
     J.flog = static_cast<double*>(h->flog.p);
 #endif
     return J;
+}
+// ... of an active call: the device list where the rows were (job_active_list)
+void set_job_active_list(job_t& J, const uint32_t* list_dev) {
+    std::memcpy(&J.row_begin, &list_dev, sizeof list_dev);
 }
 void set_pass(job_t& J, const call_pass& p) {
     J.total = p.total;
@@ -2575,6 +2835,95 @@ int emit(hipStream_t st, const call_plan& P, const rtw_render_params& R, double*
                        (uint32_t)P.npix, R.nx, R.row_begin, P.row_step, acc_dev);
     HIPCHK(hipGetLastError());
     if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(acc, acc_dev, img_bytes, hipMemcpyDeviceToHost, st));
+    return RTW_OK;
+}
+
+// An active call's pixel list and counts (rtw_render_accumulate_active).
+struct active_call {
+    const uint32_t* list = nullptr;  // the caller's, host or device as accum_on_device says
+    uint64_t n = 0;
+    uint32_t* counts = nullptr;      // may be null
+    bool checked = false;            // a device list the library's own select just wrote: no k_check_active
+};
+
+// An active call's emit: acc[list[k]] += sums[k], the same for the squares,
+// counts[list[k]] += spp, each where its pointer is set (sums null: the counts
+// alone).  Host buffers go through whole-image device copies as emit()'s do;
+// only the listed pixels change in them.
+int emit_active(handle_t* h, const rtw_render_params& R, const active_call& act, const uint32_t* list_dev, uint32_t spp,
+                double* acc, const double* sums, double* acc_sq, const double* sums_sq) {
+    hipStream_t st = h->stream;
+    const size_t img = (size_t)R.nx * R.ny * 24, cnt = img / 6;
+    double *acc_dev = sums ? acc : nullptr, *sq_dev = sums_sq ? acc_sq : nullptr;
+    uint32_t* counts_dev = act.counts;
+    if (!R.accum_on_device) {
+        if (sums) {
+            if (int rc = h->accum.ensure(img)) return rc;
+            acc_dev = static_cast<double*>(h->accum.p);
+            HIPCHK(hipMemcpyAsync(acc_dev, acc, img, hipMemcpyHostToDevice, st));
+        }
+        if (sums_sq) {
+            if (int rc = h->accum_sq.ensure(img)) return rc;
+            sq_dev = static_cast<double*>(h->accum_sq.p);
+            HIPCHK(hipMemcpyAsync(sq_dev, acc_sq, img, hipMemcpyHostToDevice, st));
+        }
+        if (act.counts) {
+            if (int rc = h->counts.ensure(cnt)) return rc;
+            counts_dev = static_cast<uint32_t*>(h->counts.p);
+            HIPCHK(hipMemcpyAsync(counts_dev, act.counts, cnt, hipMemcpyHostToDevice, st));
+        }
+    }
+    hipLaunchKernelGGL(k_emit_active, dim3(reduce_grid(act.n)), dim3(kBlock), 0, st, sums, sums_sq, (uint32_t)act.n,
+                       list_dev, spp, acc_dev, sq_dev, counts_dev);
+    HIPCHK(hipGetLastError());
+    if (!R.accum_on_device) {
+        if (sums) HIPCHK(hipMemcpyAsync(acc, acc_dev, img, hipMemcpyDeviceToHost, st));
+        if (sums_sq) HIPCHK(hipMemcpyAsync(acc_sq, sq_dev, img, hipMemcpyDeviceToHost, st));
+        if (act.counts) HIPCHK(hipMemcpyAsync(act.counts, counts_dev, cnt, hipMemcpyDeviceToHost, st));
+    }
+    return RTW_OK;
+}
+
+// The list of an active call on the device, checked: a host list is checked
+// on the host (adaptive.cpp) and copied to the handle's buffer, a device list
+// by k_check_active.  A list that is not strictly ascending or reaches past
+// the image is refused here, before any render launch.
+int active_list_device(handle_t* h, const rtw_render_params& R, const active_call& act, const uint32_t** out) {
+    hipStream_t st = h->stream;
+    const uint64_t limit = (uint64_t)R.nx * (uint64_t)R.ny;
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof a);
+    const bool known = hipPointerGetAttributes(&a, act.list) == hipSuccess;
+    if (!known) (void)hipGetLastError();
+    if (!R.accum_on_device) {
+        if (known && a.type == hipMemoryTypeDevice)
+            return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_active: a device pixel list with host buffers "
+                                             "(accum_on_device covers the list too)");
+        if (int rc = rtw_adaptive_check_list("rtw_render_accumulate_active", act.list, act.n, limit)) return rc;
+        if (int rc = h->alist.ensure(act.n * 4)) return rc;
+        HIPCHK(hipMemcpyAsync(h->alist.p, act.list, act.n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));  // (the caller's list may go after the call)
+        *out = static_cast<const uint32_t*>(h->alist.p);
+        return RTW_OK;
+    }
+    if (act.checked) {  // (rtw_render_adaptive: k_select_scatter's list is strictly ascending and in range)
+        *out = act.list;
+        return RTW_OK;
+    }
+    if (int rc = rtw_check_device_ptr(act.list, h->device, "rtw_render_accumulate_active")) return rc;
+    if (int rc = h->sel.ensure(sizeof(uint32_t) * (2 * kSelectMaxGrid + 2))) return rc;
+    uint32_t* bad = static_cast<uint32_t*>(h->sel.p);
+    HIPCHK(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_check_active, dim3(reduce_grid(act.n)), dim3(kBlock), 0, st, act.list, (uint32_t)act.n,
+                       (uint32_t)limit, bad);
+    HIPCHK(hipGetLastError());
+    uint32_t flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, bad, sizeof flag, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (flag)
+        return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_active: the device pixel list is not strictly ascending "
+                                         "or reaches past the image");
+    *out = act.list;
     return RTW_OK;
 }
 
@@ -2637,25 +2986,47 @@ int print_profile(const rtw_stats& stats) {
 // and copies, except that k_reduce_moments takes k_reduce's place and a
 // second k_emit adds the sums of squares.  With accum_sq null nothing here
 // differs from the plain render.
+// act (rtw_render_accumulate_active, rtw_adaptive.h; null: a whole-image
+// call, which launches exactly what it launched before this path existed):
+// the samples of the listed pixels.  The list takes the rows' place in the
+// plan and the job, the kernel is a row of the active lists or a wavefront
+// form refilled by k_regen_active (rtw_select.h select_active), the passes and
+// the ordered reduction run over n_active pixels, and the emit scatters.
 static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const rtw_render_params* prm,
-                             double* accum_rgb, double* accum_sq, rtw_stats* out_stats) {
+                             double* accum_rgb, double* accum_sq, rtw_stats* out_stats,
+                             const active_call* act = nullptr) {
     const rtw_render_params& R = *prm;
     // the call's plan: refusals, sizes, cameras and job fields (render_plan.h)
     call_plan P;
+    const call_active plan_act{act ? act->n : 0, act ? act->list : nullptr, act ? act->counts : nullptr};
     if (int rc = rtw_plan_call(R, *camera, h->facts, accum_rgb, accum_sq, pass_budget_samples(),
-                               RTW_STRICT_RADIANCE ? h->cus : 0, &P))
+                               RTW_STRICT_RADIANCE ? h->cus : 0, &P, act ? &plan_act : nullptr))
         return rc;
+    if (act && RTW_STRICT_RADIANCE)
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders whole images only "
+                                             "(rtw_render_accumulate_active)");
     HIPCHK(hipSetDevice(h->device));
     if (R.accum_on_device) {
         if (int rc = rtw_check_device_ptr(accum_rgb, h->device, "rtw_render_accumulate")) return rc;
         if (accum_sq)
             if (int rc = rtw_check_device_ptr(accum_sq, h->device, "rtw_render_accumulate_moments")) return rc;
+        if (act && act->counts)
+            if (int rc = rtw_check_device_ptr(act->counts, h->device, "rtw_render_accumulate_active")) return rc;
     }
     hipStream_t st = h->stream;
     rtw_stats stats;
     std::memset(&stats, 0, sizeof stats);
+    const uint32_t* list_dev = nullptr;
+    if (act && act->n)
+        if (int rc = active_list_device(h, R, *act, &list_dev)) return rc;
     if (P.noop) {
         stats.samples = P.samples;
+        // (max_depth <= 0: every sample adds zero radiance, and still counts)
+        if (act && act->n && P.spp_count && act->counts) {
+            if (int rc = emit_active(h, R, *act, list_dev, (uint32_t)P.spp_count, nullptr, nullptr, nullptr, nullptr))
+                return rc;
+            HIPCHK(hipStreamSynchronize(st));
+        }
         if (out_stats) *out_stats = stats;
         return RTW_OK;
     }
@@ -2669,8 +3040,11 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
     if (P.fast && !fast_image_ok(h))
         return rtw_fail(RTW_ERR_UNSUPPORTED, "precision fp32 with image textures covers list and world-BVH scenes only "
                                              "(this scene has media or group BVHs): render it in fp64");
+    if (act && P.fast && !active_fp32_ok(scene_facts(h, P.pin)))
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "rtw_render_accumulate_active: precision fp32 of a scene with image "
+                                             "textures has no active kernel: render it in fp64");
     plan_t plan;
-    if (int rc = plan_render(h, P.pin, P.fast, &plan)) return rc;
+    if (int rc = plan_render(h, P.pin, P.fast, &plan, act != nullptr)) return rc;
     const bool persistent = plan.c.persistent();
     if (RTW_STRICT_RADIANCE && !persistent)
         return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders with the persistent kernel only "
@@ -2700,6 +3074,7 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
     if (!ev_begin || !ev_end) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
     HIPCHK(hipEventRecord(ev_begin, st));
     job_t J = make_job(h, P, R);
+    if (act) set_job_active_list(J, list_dev);
     fast_args FA = make_fast_args(h, P);
     for (uint64_t done = 0; done < (uint64_t)P.spp_count; done += P.pass_spp) {
         const call_pass pass = rtw_plan_pass(P, R, done);
@@ -2719,9 +3094,13 @@ static int render_accumulate(handle_t* h, const rtw_camera_desc* camera, const r
         stats.samples += J.total;
     }
 
-    if (int rc = emit(st, P, R, accum_rgb, run, h->accum)) return rc;
-    if (accum_sq)
-        if (int rc = emit(st, P, R, accum_sq, run2, h->accum_sq)) return rc;
+    if (act) {
+        if (int rc = emit_active(h, R, *act, list_dev, (uint32_t)P.spp_count, accum_rgb, run, accum_sq, run2)) return rc;
+    } else {
+        if (int rc = emit(st, P, R, accum_rgb, run, h->accum)) return rc;
+        if (accum_sq)
+            if (int rc = emit(st, P, R, accum_sq, run2, h->accum_sq)) return rc;
+    }
     HIPCHK(hipMemcpyAsync(&h->host_ctrs[63], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(ev_end, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -2764,6 +3143,27 @@ extern "C" int rtw_render_accumulate_moments(void* handle, const rtw_camera_desc
     return render_accumulate(h, camera, prm, accum_rgb, accum_sq_rgb, out_stats);
 }
 
+// The summary of a launched k_noise_pixels[_counts]: the blocks' partials
+// copied out and added in block order (returns when the kernel has ended).
+static int noise_parts_summary(handle_t* h, unsigned grid, rtw_noise_summary* out) {
+    const noise_part* parts = static_cast<const noise_part*>(h->noise.p);
+    std::vector<noise_part> host(grid);
+    HIPCHK(hipMemcpyAsync(host.data(), parts, sizeof(noise_part) * grid, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (out) {
+        noise_part t = host[0];  // the blocks' partials, in block order
+        for (unsigned b = 1; b < grid; ++b) {
+            t.sum_rel = t.sum_rel + host[b].sum_rel;
+            t.sum_se2 = t.sum_se2 + host[b].sum_se2;
+            if (host[b].max_rel > t.max_rel) t.max_rel = host[b].max_rel;
+            t.pixels += host[b].pixels;
+            t.nonfinite += host[b].nonfinite;
+        }
+        rtw_noise_finish(t.pixels, t.nonfinite, t.sum_rel, t.max_rel, t.sum_se2, out);
+    }
+    return RTW_OK;
+}
+
 extern "C" int rtw_noise_estimate_device(void* handle, const double* accum, const double* accum_sq, int nx, int ny,
                                          int n, double floor, double* stderr_dev, rtw_noise_summary* out) {
     handle_t* h = static_cast<handle_t*>(handle);
@@ -2782,19 +3182,227 @@ extern "C" int rtw_noise_estimate_device(void* handle, const double* accum, cons
     hipLaunchKernelGGL(k_noise_pixels, dim3(grid), dim3(kBlock), 0, h->stream, accum, accum_sq, npix, (double)n,
                        (double)(n - 1), 3.0 * floor, stderr_dev, parts);
     HIPCHK(hipGetLastError());
-    std::vector<noise_part> host(grid);
-    HIPCHK(hipMemcpyAsync(host.data(), parts, sizeof(noise_part) * grid, hipMemcpyDeviceToHost, h->stream));
+    return noise_parts_summary(h, grid, out);
+}
+
+// ======================================================================
+// rtw_adaptive.h
+// ======================================================================
+extern "C" int rtw_render_accumulate_active(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                                            const uint32_t* active, uint64_t n_active, double* accum_rgb,
+                                            double* accum_sq_rgb, uint32_t* counts, rtw_stats* out_stats) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    if (!h || !camera || !prm || !accum_rgb || (n_active && !active))
+        return rtw_fail(RTW_ERR_INVALID, "rtw_render_accumulate_active: null argument");
+    const active_call act{active, n_active, counts};
+    return render_accumulate(h, camera, prm, accum_rgb, accum_sq_rgb, out_stats, &act);
+}
+
+extern "C" int rtw_scene_query_active(void* handle, int precision, char name[128]) {
+    const handle_t* h = static_cast<const handle_t*>(handle);
+    if (!h || !name) return rtw_fail(RTW_ERR_INVALID, "rtw_scene_query_active: null argument");
+    if (precision != RTW_PRECISION_FP64 && precision != RTW_PRECISION_FP32)
+        return rtw_fail(RTW_ERR_INVALID, "rtw_scene_query_active: unknown precision");
+    const bool fast = precision == RTW_PRECISION_FP32;
+    if (RTW_STRICT_RADIANCE)
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders whole images only");
+    if (fast && !active_fp32_ok(scene_facts(h, h->facts.desc_pin)))
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "rtw_scene_query_active: precision fp32 of a scene with image textures has "
+                                             "no active kernel");
+    HIPCHK(hipSetDevice(h->device));  // occupancy queries of the plan
+    plan_t p;
+    if (int rc = plan_render(h, h->facts.desc_pin, fast, &p, true)) return rc;
+    std::snprintf(name, 128, "%s", p.c.name.c_str());
+    return RTW_OK;
+}
+
+// The device buffers of a select / estimate / finalize call belong to the
+// handle's device.
+static int check_adaptive_ptrs(const handle_t* h, const char* what, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (p)
+            if (int rc = rtw_check_device_ptr(p, h->device, what)) return rc;
+    return RTW_OK;
+}
+
+// The select's three launches into active_dev; the length lands in *n_out
+// when the stream has run them (the caller synchronises).
+static int launch_select(handle_t* h, const double* accum, const double* accum_sq, const uint32_t* counts, uint64_t npix,
+                         double floor, double target_rel, uint32_t max_count, uint32_t* active_dev, uint32_t* n_out) {
+    if (int rc = h->sel.ensure(sizeof(uint32_t) * (2 * kSelectMaxGrid + 2))) return rc;
+    uint32_t* block_counts = static_cast<uint32_t*>(h->sel.p) + 1;  // ([0]: the list check's flag)
+    uint32_t* offsets = block_counts + kSelectMaxGrid;
+    const unsigned grid = select_grid(npix);
+    const select_args A{accum, accum_sq, counts, npix, select_chunk(npix), 3.0 * floor, target_rel, max_count};
+    hipStream_t st = h->stream;
+    hipLaunchKernelGGL(k_select_count, dim3(grid), dim3(kBlock), 0, st, A, block_counts);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(kBlock), 0, st, block_counts, (uint32_t)grid, offsets);
+    hipLaunchKernelGGL(k_select_scatter, dim3(grid), dim3(kBlock), 0, st, A, offsets, active_dev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(n_out, offsets + grid, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return RTW_OK;
+}
+
+extern "C" int rtw_adaptive_select_device(void* handle, const double* accum, const double* accum_sq,
+                                          const uint32_t* counts, int nx, int ny, double floor, double target_rel,
+                                          uint32_t max_count, uint32_t* active_dev, uint64_t* n_active_host) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    const char* const what = "rtw_adaptive_select_device";
+    if (!h) return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": null scene handle");
+    if (int rc = rtw_adaptive_check_select(what, accum, accum_sq, counts, nx, ny, floor, target_rel, active_dev,
+                                           n_active_host))
+        return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = check_adaptive_ptrs(h, what, {accum, accum_sq, counts, active_dev})) return rc;
+    uint32_t n = 0;
+    if (int rc = launch_select(h, accum, accum_sq, counts, (uint64_t)nx * (uint64_t)ny, floor, target_rel, max_count,
+                               active_dev, &n))
+        return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (out) {
-        noise_part t = host[0];  // the blocks' partials, in block order
-        for (unsigned b = 1; b < grid; ++b) {
-            t.sum_rel = t.sum_rel + host[b].sum_rel;
-            t.sum_se2 = t.sum_se2 + host[b].sum_se2;
-            if (host[b].max_rel > t.max_rel) t.max_rel = host[b].max_rel;
-            t.pixels += host[b].pixels;
-            t.nonfinite += host[b].nonfinite;
-        }
-        rtw_noise_finish(t.pixels, t.nonfinite, t.sum_rel, t.max_rel, t.sum_se2, out);
+    *n_active_host = n;
+    return RTW_OK;
+}
+
+static int estimate_counts_device(handle_t* h, const double* accum, const double* accum_sq, const uint32_t* counts,
+                                  uint64_t npix, double floor, double* stderr_dev, rtw_noise_summary* out) {
+    const unsigned grid = noise_grid(npix);
+    if (int rc = h->noise.ensure(sizeof(noise_part) * kNoiseMaxGrid)) return rc;
+    hipLaunchKernelGGL(k_noise_pixels_counts, dim3(grid), dim3(kBlock), 0, h->stream, accum, accum_sq, counts, npix,
+                       3.0 * floor, stderr_dev, static_cast<noise_part*>(h->noise.p));
+    HIPCHK(hipGetLastError());
+    return noise_parts_summary(h, grid, out);
+}
+
+extern "C" int rtw_noise_estimate_counts_device(void* handle, const double* accum, const double* accum_sq,
+                                                const uint32_t* counts, int nx, int ny, double floor,
+                                                double* stderr_dev, rtw_noise_summary* out) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    const char* const what = "rtw_noise_estimate_counts_device";
+    if (!h) return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": null scene handle");
+    if (int rc = rtw_adaptive_check_estimate(what, accum, accum_sq, counts, nx, ny, floor, stderr_dev)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = check_adaptive_ptrs(h, what, {accum, accum_sq, counts, stderr_dev})) return rc;
+    return estimate_counts_device(h, accum, accum_sq, counts, (uint64_t)nx * (uint64_t)ny, floor, stderr_dev, out);
+}
+
+extern "C" int rtw_finalize_canvas_counts_device(void* handle, const double* accum, const uint32_t* counts, int nx,
+                                                 int ny, double* canvas) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    const char* const what = "rtw_finalize_canvas_counts_device";
+    if (!h || !accum || !counts || !canvas || nx <= 0 || ny <= 0)
+        return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = check_adaptive_ptrs(h, what, {accum, counts, canvas})) return rc;
+    const size_t n = (size_t)nx * (size_t)ny * 3;
+    hipLaunchKernelGGL(k_finalize_counts, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, accum, counts, n, canvas);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return RTW_OK;
+}
+
+static void add_stats(rtw_stats& t, const rtw_stats& s) {
+    t.samples += s.samples, t.segments += s.segments, t.iterations += s.iterations;
+    t.launches_intersect += s.launches_intersect;
+    t.ms_total += s.ms_total, t.ms_intersect += s.ms_intersect, t.ms_shade += s.ms_shade;
+    t.ms_finalize += s.ms_finalize, t.bytes_intersect += s.bytes_intersect;
+}
+
+// The adaptive loop: the schedule is rtw_adaptive_next_round (adaptive.cpp),
+// the rounds are this file's own render, select and estimate on device
+// buffers -- the caller's, or the handle's when the caller's are host memory
+// (copied out once at the end).
+extern "C" int rtw_render_adaptive(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                                   const rtw_adaptive_params* ap, double* accum_rgb, double* accum_sq_rgb,
+                                   uint32_t* counts, rtw_adaptive_result* out_result, rtw_stats* out_stats) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    const char* const what = "rtw_render_adaptive";
+    if (!h || !camera || !prm || !accum_rgb || !accum_sq_rgb || !counts)
+        return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": null argument");
+    if (int rc = rtw_adaptive_check_params(what, ap)) return rc;
+    if (RTW_STRICT_RADIANCE)
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders whole images only (rtw_render_adaptive)");
+    if (prm->nx <= 0 || prm->ny <= 0 || (uint64_t)prm->nx * (uint64_t)prm->ny >= (1ull << 31))
+        return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": bad image size");
+    const uint64_t npix = (uint64_t)prm->nx * (uint64_t)prm->ny;
+    const size_t img = npix * 24, cnt = npix * 4;
+    if (rtw_ranges_overlap(accum_rgb, accum_sq_rgb, img) || rtw_spans_overlap(counts, cnt, accum_rgb, img) ||
+        rtw_spans_overlap(counts, cnt, accum_sq_rgb, img))
+        return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": two of the buffers overlap");
+    HIPCHK(hipSetDevice(h->device));
+    const bool on_device = prm->accum_on_device != 0;
+    double *a_dev = accum_rgb, *q_dev = accum_sq_rgb;
+    uint32_t* c_dev = counts;
+    if (on_device) {
+        if (int rc = check_adaptive_ptrs(h, what, {accum_rgb, accum_sq_rgb, counts})) return rc;
+    } else {
+        if (int rc = h->accum.ensure(img)) return rc;
+        if (int rc = h->accum_sq.ensure(img)) return rc;
+        if (int rc = h->counts.ensure(cnt)) return rc;
+        a_dev = static_cast<double*>(h->accum.p), q_dev = static_cast<double*>(h->accum_sq.p);
+        c_dev = static_cast<uint32_t*>(h->counts.p);
     }
+    if (int rc = h->alist.ensure(cnt)) return rc;
+    uint32_t* list = static_cast<uint32_t*>(h->alist.p);
+    hipStream_t st = h->stream;
+    HIPCHK(hipMemsetAsync(a_dev, 0, img, st));
+    HIPCHK(hipMemsetAsync(q_dev, 0, img, st));
+
+    rtw_render_params R = *prm;  // every round renders on the device buffers
+    R.spp = ap->max_spp, R.row_begin = 0, R.row_step = 1, R.accum_on_device = 1;
+    rtw_stats total, s;
+    std::memset(&total, 0, sizeof total);
+    rtw_adaptive_result res;
+    std::memset(&res, 0, sizeof res);
+    int done = 0;
+    for (;;) {
+        int begin = 0, count = 0;
+        if (int rc = rtw_adaptive_next_round(ap, done, &begin, &count)) return rc;
+        if (count == 0) break;
+        R.spp_begin = begin, R.spp_count = count;
+        if (done == 0) {
+            // round 0: every pixel, through the whole-image render
+            if (int rc = render_accumulate(h, camera, &R, a_dev, q_dev, &s)) return rc;
+            hipLaunchKernelGGL(k_set_counts, dim3(grid_for(npix)), dim3(kBlock), 0, st, c_dev, (size_t)npix,
+                               (uint32_t)count);
+            HIPCHK(hipGetLastError());
+        } else {
+            uint32_t n = 0;
+            if (int rc = launch_select(h, a_dev, q_dev, c_dev, npix, ap->floor, ap->target_rel, (uint32_t)ap->max_spp,
+                                       list, &n))
+                return rc;
+            HIPCHK(hipStreamSynchronize(st));
+            if (n == 0) break;
+            const active_call act{list, n, c_dev, true};
+            if (int rc = render_accumulate(h, camera, &R, a_dev, q_dev, &s, &act)) return rc;
+        }
+        add_stats(total, s);
+        done += count;
+        ++res.rounds;
+    }
+    // the summary is the estimate of the buffers the caller gets back: the
+    // device estimator's for device buffers, the host's for host buffers
+    if (on_device)
+        if (int rc = estimate_counts_device(h, a_dev, q_dev, c_dev, npix, ap->floor, nullptr, &res.final)) return rc;
+    std::vector<uint32_t> c_host;
+    uint32_t* c_read = counts;
+    if (on_device) {
+        c_host.resize(npix);
+        c_read = c_host.data();
+    } else {
+        HIPCHK(hipMemcpyAsync(accum_rgb, a_dev, img, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(accum_sq_rgb, q_dev, img, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipMemcpyAsync(c_read, c_dev, cnt, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!on_device)
+        if (int rc = rtw_noise_estimate_counts(accum_rgb, accum_sq_rgb, counts, prm->nx, prm->ny, ap->floor, nullptr,
+                                               &res.final))
+            return rc;
+    for (uint64_t p = 0; p < npix; ++p) {
+        res.samples += c_read[p];
+        res.pixels_at_max += c_read[p] == (uint32_t)ap->max_spp ? 1 : 0;
+    }
+    if (out_result) *out_result = res;
+    if (out_stats) *out_stats = total;
     return RTW_OK;
 }

@@ -30,7 +30,12 @@ enum : int { F_MEDIA = 1, F_WBVH = 2, F_GBVH = 4, F_YSPH = 8, F_STATIC = 16, F_L
              // every camera ray of the render starts at the camera's origin (a
              // pinhole camera, lens_radius 0, whose origin has no zero
              // coordinate: origin + offset is then exactly origin, camera.h:48)
-             F_PIN = 256 };
+             F_PIN = 256,
+             // the render lists its pixels (rtw_adaptive.h): the camera sample's
+             // pixel is read from the active list (rtw_kernels.hip sample_coords).
+             // Only the instantiations of the active lists below carry the bit;
+             // it is free in the FF_* range of the fp32 kernels too.
+             F_ACTIVE = 512 };
 // fp32 kernels for scenes without a noise texture (F bit, fast kernels only):
 // the marble texture compiled out of shading (rtw_fast.h texture_value)
 constexpr int FF_NONOISE = 1 << 12;
@@ -104,8 +109,8 @@ struct inst {
 };
 constexpr bool operator==(const inst& a, const inst& b) { return a.f == b.f && a.m == b.m && a.l == b.l; }
 
-template <class L>
-constexpr int index_of(const L& list, const inst& x) {
+template <class L, class X>
+constexpr int index_of(const L& list, const X& x) {
     for (size_t k = 0; k < list.size(); ++k)
         if (list[k] == x) return (int)k;
     return -1;
@@ -198,6 +203,39 @@ constexpr inst kFastFallback = kFastList[0];
 #endif
 
 // ---- the choice --------------------------------------------------------------
+enum class kform { persist_sort, persist, persist_lst, segment, split, fast, fast_sort };
+
+// Kernels with the active-pixel indirection (F_ACTIVE, rtw_adaptive.h).  A row
+// names ONE kernel form, not the three a kPersistList entry expands to: the
+// kernels the built-in scenes select by default, each in the form that scene
+// runs.  Every other fp64 render of a pixel list takes the wavefront forms,
+// where k_regen_active is the only kernel that makes camera rays.
+struct active_inst {
+    inst id;
+    kform form;
+};
+constexpr bool operator==(const active_inst& a, const active_inst& b) { return a.id == b.id && a.form == b.form; }
+#if !defined(RTW_SUBSET) && !defined(RTW_SUBSET_FAST) && !(defined(RTW_STRICT_RADIANCE) && RTW_STRICT_RADIANCE)
+constexpr std::array kPersistActiveList{
+    active_inst{{F_STATIC | F_LIGHTS | F_BLACK | F_ACTIVE, SF_DIEL, true}, kform::persist_sort},          // Cornell
+    active_inst{{F_YSPH | F_NOLIGHTS | F_ACTIVE, SF_METAL | SF_DIEL, false}, kform::persist_sort},        // random_balls
+    active_inst{{F_WBVH | F_NOLIGHTS | F_ACTIVE, SF_METAL | SF_DIEL, false}, kform::persist_lst},         // ... with a BVH
+    active_inst{{F_MEDIA | F_GBVH | F_LIGHTS | F_BLACK | F_PIN | F_ACTIVE, SF_NOCHECKER, false}, kform::persist_lst}};  // Book 2 with BVHs
+// fp32 is always persistent: the built-in scenes' rows, then one general
+// k_fast per traversal walk (rtw_fast.h world_closest has three: world BVH,
+// media, list; F_GBVH is tested per entry at run time, the marble texture is
+// compiled in), which render every scene of their walk to the same bits.
+constexpr std::array kFastActiveList{
+    active_inst{{F_WBVH | FF_NONOISE | F_ACTIVE, -1, true}, kform::fast},   // random_balls + BVH
+    active_inst{{F_MEDIA | F_GBVH | F_ACTIVE, -1, true}, kform::fast},      // Book 2 with BVHs
+    active_inst{{F_GBVH | F_ACTIVE, -1, false}, kform::fast}, active_inst{{F_WBVH | F_GBVH | F_ACTIVE, -1, false}, kform::fast},
+    active_inst{{F_MEDIA | F_GBVH | F_ACTIVE, -1, false}, kform::fast}};
+constexpr std::array kFastSortActiveList{active_inst{{FF_NONOISE | F_ACTIVE, -1, true}, kform::fast_sort},    // Cornell
+                                         active_inst{{FF_NONOISE | F_ACTIVE, -1, false}, kform::fast_sort}};  // random_balls
+#else  // experiment builds and the strict-radiance build (which refuses every active call) render whole images only
+constexpr std::array<active_inst, 0> kPersistActiveList{}, kFastActiveList{}, kFastSortActiveList{};
+#endif
+
 struct select_env {
     bool wavefront = false;  // RTW_MODE=wavefront: no persistent kernel (fp64)
     bool split = false;      // RTW_SPLIT=1: k_intersect + k_shade, not k_segment
@@ -216,14 +254,14 @@ struct select_in {
     bool ysph = false, static_scene = false, lights = false, black = false, pin = false;
     select_env env;
     bool strict = false;  // RTW_STRICT_RADIANCE build: folds each path's factors in k_persist, never sorts
+    bool active = false;  // the render lists its pixels (rtw_render_accumulate_active): select_active
 };
-
-enum class kform { persist_sort, persist, persist_lst, segment, split, fast, fast_sort };
 
 struct kernel_choice {
     kform form;
     inst id;  // the template arguments; split: {features, shade set, LDS shading}, the rows by split_resolve
     std::string name;
+    bool active = false;  // select_active's: a row of the active lists, or a wavefront form refilled by k_regen_active
     bool persistent() const { return form != kform::segment && form != kform::split; }
 };
 
@@ -248,7 +286,9 @@ inline kernel_choice persist_choice(const inst& c, const select_in& s) {
 // textures has one candidate.  Without a persistent instantiation: the fused
 // k_segment where listed (and RTW_SPLIT is not set), else the split pair,
 // which covers everything and is reported as k_intersect<features>.
+inline kernel_choice select_active(const select_in& s, bool fp32);  // (a render of a pixel list: below)
 inline kernel_choice select_fp64(const select_in& s) {
+    if (s.active) return select_active(s, false);
     const int pick = pick_shade_mask(s.shade_mask);
     const bool image = (pick & SF_IMAGE) != 0;  // (no LDS form for image scenes)
     const bool lds = !image && s.shade_bytes <= kShadeLdsMax;
@@ -293,6 +333,7 @@ inline split_rows split_resolve(const inst& id) {
 // stacks when the deepest walk fits them; a feature set without a row runs
 // kFastFallback.
 inline kernel_choice select_fp32(const select_in& s) {
+    if (s.active) return select_active(s, true);
     const int f = s.features & (F_MEDIA | F_WBVH | F_GBVH);
     const bool bvh = (f & (F_WBVH | F_GBVH)) != 0;
     kform form = kform::fast;
@@ -317,6 +358,42 @@ inline kernel_choice select_fp32(const select_in& s) {
     if ((form == kform::fast_sort ? index_of(kFastSortList, c) : index_of(kFastList, c)) < 0)
         form = kform::fast, c = kFastFallback;
     return {form, c, kname(form == kform::fast ? "k_fast" : "k_fast_sort", c.f, -1, c.l)};
+}
+
+// A render of a pixel list (s.active).  The kernel the whole-image render of
+// the same scene runs, with F_ACTIVE, where the active lists hold it in that
+// form.  Else fp64: the wavefront forms as select_fp64 picks them under
+// RTW_MODE=wavefront (k_segment where listed and RTW_SPLIT is unset, else the
+// split pair), named with the k_regen_active that refills them; fp32: the
+// general k_fast of the scene's walk.  fp32 renders of image-texture scenes
+// have no active kernel (active_fp32_ok: refused before any launch).
+inline bool active_fp32_ok(const select_in& s) { return !(s.shade_mask & SF_IMAGE); }
+inline kernel_choice select_active(const select_in& s_in, bool fp32) {
+    select_in s = s_in;
+    s.active = false;
+    const kernel_choice c = fp32 ? select_fp32(s) : select_fp64(s);
+    const active_inst want{{c.id.f | F_ACTIVE, c.id.m, c.id.l}, c.form};
+    const char* const fam = c.form == kform::persist_sort ? "k_persist_sort"
+                            : c.form == kform::fast       ? "k_fast"
+                            : c.form == kform::fast_sort  ? "k_fast_sort" : "k_persist";
+    const int lst = c.form == kform::persist ? 0 : c.form == kform::persist_lst ? 1 : -1;
+    if (fp32) {
+        if (c.form == kform::fast_sort ? index_of(kFastSortActiveList, want) >= 0 : index_of(kFastActiveList, want) >= 0)
+            return {c.form, want.id, kname(fam, want.id.f, -1, want.id.l), true};
+        // (a build with empty active lists has no such row.  The strict build never gets here: its entry points
+        // refuse an active call with RTW_ERR_UNSUPPORTED before anything selects.  In an RTW_SUBSET experiment
+        // build plan_render answers this choice with "no such instantiation", an error, not a launch.)
+        const int f = s.features & (F_MEDIA | F_WBVH | F_GBVH);
+        const inst g{((f & F_MEDIA) ? F_MEDIA : (f & F_WBVH) ? F_WBVH : 0) | F_GBVH | F_ACTIVE, -1, false};
+        return {kform::fast, g, kname("k_fast", g.f, -1, g.l), true};
+    }
+    if (!s.strict && c.persistent() && index_of(kPersistActiveList, want) >= 0)
+        return {c.form, want.id, kname(fam, want.id.f, want.id.m, want.id.l, lst), true};
+    s.env.wavefront = true;
+    kernel_choice w = select_fp64(s);
+    w.name = "k_regen_active + " + w.name;
+    w.active = true;
+    return w;
 }
 
 }  // namespace rtwd

@@ -7,12 +7,19 @@
 //              [--depth 100] [--seed 0] [--bvh] [--device 0] [--gpus 1]
 //              [--precision fp64|fp32] [--out out.ppm] [--image FILE.ppm]
 //              [--noise] [--noise-target X [--noise-batch 8] [--noise-floor 0.01]]
+//              [--adaptive X [--min-spp 16] [--noise-batch B] [--noise-floor 0.01]]
 //
 // --noise renders through rtw_render_accumulate_moments (rtw_noise.h) and
 // prints the image-wide noise estimate of the --spp samples.  --noise-target X
 // renders the sample ranges [0,b) [b,2b) [2b,4b) ... (b = --noise-batch) until
 // the estimate's mean relative standard error is at most X or --spp samples
 // are done, and finalizes the canvas with the samples it used.  One GPU only.
+//
+// --adaptive X renders through rtw_render_adaptive (rtw_adaptive.h): --min-spp
+// samples of every pixel, then rounds of --noise-batch samples (not given: as
+// many as are done so far) of the pixels whose relative standard error is
+// still above X, with --spp as the most a pixel takes; the canvas divides
+// every pixel's sum by its own sample count.  One GPU only.
 //
 // --image FILE.ppm (with --scene textured): a P6 or P3 PPM, maxval 255, that
 // replaces the scene's first image texture (rtw_load_ppm).
@@ -34,6 +41,7 @@
 #include <vector>
 #include "rtw/scene.h"
 #include "rtw_gpu.h"
+#include "rtw_adaptive.h"
 #include "rtw_noise.h"
 
 int main(int argc, char** argv) {
@@ -42,7 +50,9 @@ int main(int argc, char** argv) {
     unsigned long long seed = 0;
     bool noise = false, to_target = false;
     double noise_target = 0.0, noise_floor = 1e-2;
-    int noise_batch = 8;
+    int noise_batch = 8, min_spp = 16;
+    bool adaptive = false, batch_given = false;
+    double adaptive_target = 0.0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -65,7 +75,9 @@ int main(int argc, char** argv) {
         else if (a == "--image") image = next();
         else if (a == "--noise") noise = true;
         else if (a == "--noise-target") noise_target = std::atof(next()), noise = to_target = true;
-        else if (a == "--noise-batch") noise_batch = std::atoi(next());
+        else if (a == "--noise-batch") noise_batch = std::atoi(next()), batch_given = true;
+        else if (a == "--adaptive") adaptive_target = std::atof(next()), adaptive = true;
+        else if (a == "--min-spp") min_spp = std::atoi(next());
         else if (a == "--noise-floor") noise_floor = std::atof(next());
         else if (a == "--precision") {
             const std::string v = next();
@@ -88,6 +100,17 @@ int main(int argc, char** argv) {
     }
     if (noise && (spp < 2 || noise_batch < 2 || (to_target && !(noise_target > 0.0)) || !(noise_floor > 0.0))) {
         std::fprintf(stderr, "--noise needs --spp >= 2, --noise-batch >= 2, --noise-target > 0, --noise-floor > 0\n");
+        return 2;
+    }
+
+    if (adaptive && (gpus != 1 || noise)) {
+        std::fprintf(stderr, "--adaptive renders on one GPU (--gpus 1), without --noise / --noise-target\n");
+        return 2;
+    }
+    if (adaptive && (!(adaptive_target >= 0.0) || min_spp < 2 || spp < min_spp || (batch_given && noise_batch < 1) ||
+                     !(noise_floor > 0.0))) {
+        std::fprintf(stderr, "--adaptive needs a target >= 0, --min-spp >= 2, --spp >= --min-spp, --noise-batch >= 1, "
+                             "--noise-floor > 0\n");
         return 2;
     }
 
@@ -137,8 +160,22 @@ int main(int argc, char** argv) {
     int spp_done = spp;
     rtw_noise_summary ns;
     std::memset(&ns, 0, sizeof ns);
+    rtw_adaptive_result ar;
+    std::memset(&ar, 0, sizeof ar);
+    std::vector<uint32_t> counts;
     auto t0 = std::chrono::high_resolution_clock::now();
-    if (noise) {
+    if (adaptive) {
+        std::vector<double> accum_sq(accum.size(), 0.0);
+        counts.assign((size_t)nx * ny, 0u);
+        rtw_adaptive_params ap;
+        std::memset(&ap, 0, sizeof ap);
+        ap.target_rel = adaptive_target, ap.floor = noise_floor, ap.min_spp = min_spp, ap.max_spp = spp;
+        ap.batch = batch_given ? noise_batch : 0;
+        if (rtw_render_adaptive(h[0], &cam, &p, &ap, accum.data(), accum_sq.data(), counts.data(), &ar, &st) != RTW_OK) {
+            std::fprintf(stderr, "render: %s\n", rtw_last_error());
+            return 1;
+        }
+    } else if (noise) {
         // one batch of all samples, or (--noise-target) batches that double the
         // total until the estimate reaches the target (render.render_to_noise)
         std::vector<double> accum_sq(accum.size(), 0.0);
@@ -169,7 +206,8 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    rtw_finalize_canvas(accum.data(), nx, ny, spp_done, canvas.data());
+    if (adaptive) rtw_finalize_canvas_counts(accum.data(), counts.data(), nx, ny, canvas.data());
+    else rtw_finalize_canvas(accum.data(), nx, ny, spp_done, canvas.data());
     auto t1 = std::chrono::high_resolution_clock::now();
     if (rtw_write_ppm(out.c_str(), canvas.data(), nx, ny) != RTW_OK) {
         std::fprintf(stderr, "write: %s\n", rtw_last_error());
@@ -185,6 +223,10 @@ int main(int argc, char** argv) {
     if (noise)
         std::printf("Noise: spp %d of %d  mean_rel %.6e  max_rel %.6e  rms_stderr %.6e\n", spp_done, spp,
                     ns.mean_rel, ns.max_rel, ns.rms_stderr);
+    if (adaptive)
+        std::printf("Adaptive: rounds %u  samples %llu of %llu  mean_rel %.6e  max_rel %.6e  at_max %llu\n", ar.rounds,
+                    (unsigned long long)ar.samples, (unsigned long long)nx * ny * spp, ar.final.mean_rel,
+                    ar.final.max_rel, (unsigned long long)ar.pixels_at_max);
     for (void* x : h) rtw_scene_free(x);
     if (gpus > 1) rtw_release_communicators();
     rtw_scene_desc_free(desc);

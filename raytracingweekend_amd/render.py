@@ -163,6 +163,114 @@ class DeviceScene:
               "rtw_noise_estimate_device")
         return se, out.as_dict()
 
+    # ---- adaptive sampling (include/rtw_adaptive.h) ---------------------------
+    def _u32_ptr(self, a, n: int, name: str, want_device: bool):
+        """Pointer of a uint32 buffer of `n` entries of the same kind as the
+        moments: numpy, or a torch tensor on this device (int32 is accepted:
+        torch has no unsigned 32-bit arithmetic; the values are below 2^31)."""
+        if isinstance(a, np.ndarray):
+            if want_device:
+                raise ValueError(f"{name} must be a torch tensor on this device, like the moments")
+            if a.dtype != np.uint32 or a.size != n or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{name} must be a contiguous uint32 array of {n} entries")
+            return a.ctypes.data_as(C.c_void_p)
+        import torch
+        if not want_device:
+            raise ValueError(f"{name} must be a numpy array, like the moments")
+        if a.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or a.numel() != n \
+                or not a.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 tensor of {n} entries")
+        if not a.is_cuda or a.device.index != self.device:
+            raise ValueError(f"a torch {name} must live on this scene's GPU (cuda:{self.device})")
+        torch.cuda.synchronize(a.device)
+        return C.c_void_p(a.data_ptr())
+
+    def render_active(self, nx: int, ny: int, spp: int, max_depth: int, seed: int = 0, *, active, accum, accum_sq=None,
+                      counts=None, spp_begin: int = 0, spp_count: int = 0, row_begin: int = 0, row_step: int = 1,
+                      camera: Optional[_abi.rtw_camera_desc] = None, collect_kernel_times: bool = False,
+                      wavefront_paths: int = 0, precision: str = "fp64"):
+        """rtw_render_accumulate_active: the samples [spp_begin, spp_begin +
+        spp_count) of the pixels listed in `active` (indices j*nx + i,
+        strictly ascending), added to those pixels of `accum`, `accum_sq`
+        (optional) and, as a sample count, `counts` (optional).  All buffers
+        are numpy arrays (uint32 list and counts) or all torch tensors on this
+        device (int32 list and counts).  Returns the stats dict."""
+        on_device = not isinstance(accum, np.ndarray)
+        ptr, _ = self._accum_ptr(accum, nx, ny, "accum")
+        ptr_sq = None
+        if accum_sq is not None:
+            _, ptr_sq, _ = self._moment_buffers(accum, accum_sq, nx, ny)
+        n_active = int(active.size if isinstance(active, np.ndarray) else active.numel())
+        ptr_list = self._u32_ptr(active, n_active, "active", on_device)
+        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", on_device) if counts is not None else None
+        prm = _abi.rtw_render_params(nx=nx, ny=ny, spp=spp, max_depth=max_depth, seed=seed, spp_begin=spp_begin,
+                                     spp_count=spp_count, row_begin=row_begin, row_step=row_step,
+                                     accum_on_device=int(on_device), collect_kernel_times=int(collect_kernel_times),
+                                     wavefront_paths=wavefront_paths, precision=_precision(precision))
+        st = _abi.rtw_stats()
+        cam = camera if camera is not None else self.scene.camera
+        check(lib().rtw_render_accumulate_active(self.handle, C.byref(cam), C.byref(prm), ptr_list, n_active, ptr,
+                                                 ptr_sq, ptr_counts, C.byref(st)), "rtw_render_accumulate_active")
+        return st.as_dict()
+
+    def select_active(self, accum, accum_sq, counts, nx: int, ny: int, *, target_rel: float, max_count: int,
+                      floor: float = 1e-2):
+        """The ascending list of the active pixels (rtw_adaptive.h): torch
+        tensors on this device go through rtw_adaptive_select_device and give
+        an int32 tensor, numpy arrays through the host function,
+        render.select_active."""
+        if isinstance(accum, np.ndarray):
+            return select_active(accum, accum_sq, counts, nx, ny, target_rel=target_rel, max_count=max_count,
+                                 floor=floor)
+        import torch
+        ptr, ptr_sq, _ = self._moment_buffers(accum, accum_sq, nx, ny)
+        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", True)
+        out = torch.empty(nx * ny, dtype=torch.int32, device=accum.device)
+        torch.cuda.synchronize(accum.device)
+        n = C.c_uint64()
+        check(lib().rtw_adaptive_select_device(self.handle, ptr, ptr_sq, ptr_counts, nx, ny, floor, target_rel,
+                                               max_count, C.c_void_p(out.data_ptr()), C.byref(n)),
+              "rtw_adaptive_select_device")
+        return out[:n.value]
+
+    def noise_estimate_counts(self, accum, accum_sq, counts, nx: int, ny: int, floor: float = 1e-2,
+                              want_stderr: bool = True):
+        """noise_estimate with a per-pixel sample count (rtw_noise_estimate_counts
+        [_device]).  Returns (stderr or None, summary dict)."""
+        if isinstance(accum, np.ndarray):
+            return noise_estimate_counts(accum, accum_sq, counts, nx, ny, floor, want_stderr)
+        import torch
+        ptr, ptr_sq, _ = self._moment_buffers(accum, accum_sq, nx, ny)
+        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", True)
+        se = torch.empty_like(accum) if want_stderr else None
+        out = _abi.rtw_noise_summary()
+        check(lib().rtw_noise_estimate_counts_device(self.handle, ptr, ptr_sq, ptr_counts, nx, ny, floor,
+                                                     C.c_void_p(se.data_ptr()) if want_stderr else None,
+                                                     C.byref(out)), "rtw_noise_estimate_counts_device")
+        return se, out.as_dict()
+
+    def finalize_counts(self, accum, counts, nx: int, ny: int):
+        """canvas = min(sqrt(accum / counts[p]), 1) (rtw_finalize_canvas_counts
+        [_device]): a tensor for tensors, an array for arrays."""
+        if isinstance(accum, np.ndarray):
+            return finalize_counts(accum, counts, nx, ny)
+        import torch
+        ptr, _ = self._accum_ptr(accum, nx, ny, "accum")
+        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", True)
+        canvas = torch.empty_like(accum)
+        torch.cuda.synchronize(accum.device)
+        check(lib().rtw_finalize_canvas_counts_device(self.handle, ptr, ptr_counts, nx, ny,
+                                                      C.c_void_p(canvas.data_ptr())),
+              "rtw_finalize_canvas_counts_device")
+        return canvas
+
+    def query_active(self, precision: str = "fp64") -> str:
+        """rtw_scene_query_active: the traversal kernel an active render of
+        this scene launches now."""
+        name = C.create_string_buffer(128)
+        check(lib().rtw_scene_query_active(self.handle, _precision(precision), name), "rtw_scene_query_active")
+        return name.value.decode()
+
     def finalize_device(self, accum, nx: int, ny: int, spp: int, canvas=None):
         """canvas = min(sqrt(accum / spp), 1) on the GPU (torch float64 CUDA
         tensors of nx*ny*3 on this device).  Returns the canvas tensor."""
@@ -344,6 +452,121 @@ def render_to_noise(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: in
         reached = summary["mean_rel"] <= target
     return {"accum": accum, "accum_sq": accum_sq, "spp_done": done, "reached": reached, "history": history,
             "stats": stats}
+
+
+def _moments_counts(accum, accum_sq, counts, nx: int, ny: int):
+    a = np.ascontiguousarray(accum, dtype=np.float64)
+    q = np.ascontiguousarray(accum_sq, dtype=np.float64) if accum_sq is not None else None
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if a.size != nx * ny * 3 or (q is not None and q.size != nx * ny * 3) or c.size != nx * ny:
+        raise ValueError("the moments must hold nx*ny*3 values and counts nx*ny")
+    return a, q, c
+
+
+def select_active(accum, accum_sq, counts, nx: int, ny: int, *, target_rel: float, max_count: int,
+                  floor: float = 1e-2) -> np.ndarray:
+    """rtw_adaptive_select on the host: the ascending uint32 list of the pixels
+    with counts < max_count, finite moments and (counts < 2 or rel > target_rel)
+    (include/rtw_adaptive.h)."""
+    a, q, c = _moments_counts(accum, accum_sq, counts, nx, ny)
+    out = np.empty(nx * ny, dtype=np.uint32)
+    n = C.c_uint64()
+    check(lib().rtw_adaptive_select(a.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p),
+                                    c.ctypes.data_as(C.c_void_p), nx, ny, floor, target_rel, max_count,
+                                    out.ctypes.data_as(C.c_void_p), C.byref(n)), "rtw_adaptive_select")
+    return out[:n.value].copy()
+
+
+def noise_estimate_counts(accum, accum_sq, counts, nx: int, ny: int, floor: float = 1e-2, want_stderr: bool = True):
+    """rtw_noise_estimate_counts on the host: noise_estimate with each pixel's
+    own sample count; pixels with fewer than two samples are left out (counted
+    in `nonfinite`).  Returns (stderr array or None, summary dict)."""
+    a, q, c = _moments_counts(accum, accum_sq, counts, nx, ny)
+    se = np.empty(nx * ny * 3, dtype=np.float64) if want_stderr else None
+    out = _abi.rtw_noise_summary()
+    check(lib().rtw_noise_estimate_counts(a.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p),
+                                          c.ctypes.data_as(C.c_void_p), nx, ny, floor,
+                                          se.ctypes.data_as(C.c_void_p) if want_stderr else None, C.byref(out)),
+          "rtw_noise_estimate_counts")
+    return se, out.as_dict()
+
+
+def finalize_counts(accum, counts, nx: int, ny: int) -> np.ndarray:
+    """canvas = min(sqrt(sum / counts[p]), 1) via rtw_finalize_canvas_counts."""
+    a, _, c = _moments_counts(accum, None, counts, nx, ny)
+    out = np.empty(nx * ny * 3, dtype=np.float64)
+    check(lib().rtw_finalize_canvas_counts(a.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), nx, ny,
+                                           out.ctypes.data_as(C.c_void_p)), "rtw_finalize_canvas_counts")
+    return out
+
+
+def _adaptive_params(target_rel: float, floor: float, min_spp: int, max_spp: int, batch: int):
+    if min_spp < 2:
+        raise ValueError("min_spp must be at least 2 (a variance needs two samples)")
+    if max_spp < min_spp:
+        raise ValueError("max_spp must be at least min_spp")
+    if batch < 0:
+        raise ValueError("batch must not be negative (0: each round doubles the samples)")
+    if not target_rel >= 0:
+        raise ValueError("target_rel must not be negative")
+    if not floor > 0:
+        raise ValueError("floor must be positive")
+    return _abi.rtw_adaptive_params(target_rel=target_rel, floor=floor, min_spp=min_spp, max_spp=max_spp, batch=batch)
+
+
+def adaptive_schedule(min_spp: int, max_spp: int, batch: int = 0):
+    """Every round's (begin, count) of the adaptive loop, from the library's
+    rtw_adaptive_next_round: [0, min_spp), then `batch` samples a round
+    (batch 0: as many as are done, doubling), the last cut at max_spp."""
+    ap = _adaptive_params(0.0, 1.0, min_spp, max_spp, batch)
+    rounds, done = [], 0
+    while True:
+        b, c = C.c_int(), C.c_int()
+        check(lib().rtw_adaptive_next_round(C.byref(ap), done, C.byref(b), C.byref(c)), "rtw_adaptive_next_round")
+        if c.value == 0:
+            return rounds
+        rounds.append((b.value, c.value))
+        done = b.value + c.value
+
+
+def render_adaptive(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: int = 0, *, target_rel: float,
+                    min_spp: int = 16, batch: int = 0, floor: float = 1e-2, precision: str = "fp64",
+                    device_buffers: bool = False, camera=None) -> dict:
+    """Adaptive per-pixel sampling, the library's loop (rtw_render_adaptive):
+    [0, min_spp) of every pixel, then rounds of `batch` samples (0: doubling)
+    of the pixels whose relative standard error is still above target_rel,
+    until none is or max_spp samples are done.  A pixel stopped on the variance
+    of its own samples is biased low where it is dark and heavy-tailed: that
+    is what min_spp is for (include/rtw_adaptive.h).
+
+    Returns a dict: accum, accum_sq (float64), counts (uint32 array, or int32
+    tensor with device_buffers), rounds, samples, pixels_at_max, summary
+    (noise_estimate_counts of the result), history (per round: (begin, count,
+    pixels rendered), read from the schedule and the counts) and stats."""
+    ap = _adaptive_params(target_rel, floor, min_spp, max_spp, batch)
+    if device_buffers:
+        import torch
+        accum = torch.zeros(nx * ny * 3, dtype=torch.float64, device=f"cuda:{ds.device}")
+        accum_sq = torch.zeros_like(accum)
+        counts = torch.zeros(nx * ny, dtype=torch.int32, device=accum.device)
+        torch.cuda.synchronize(accum.device)
+        ptrs = [C.c_void_p(t.data_ptr()) for t in (accum, accum_sq, counts)]
+    else:
+        accum = np.zeros(nx * ny * 3, dtype=np.float64)
+        accum_sq = np.zeros_like(accum)
+        counts = np.zeros(nx * ny, dtype=np.uint32)
+        ptrs = [a.ctypes.data_as(C.c_void_p) for a in (accum, accum_sq, counts)]
+    prm = _abi.rtw_render_params(nx=nx, ny=ny, spp=max_spp, max_depth=max_depth, seed=seed, row_step=1,
+                                 accum_on_device=int(device_buffers), precision=_precision(precision))
+    res, st = _abi.rtw_adaptive_result(), _abi.rtw_stats()
+    cam = camera if camera is not None else ds.scene.camera
+    check(lib().rtw_render_adaptive(ds.handle, C.byref(cam), C.byref(prm), C.byref(ap), *ptrs, C.byref(res),
+                                    C.byref(st)), "rtw_render_adaptive")
+    c_host = counts if isinstance(counts, np.ndarray) else counts.cpu().numpy()
+    history = [(b, c, int((c_host > b).sum())) for b, c in adaptive_schedule(min_spp, max_spp, batch)[:res.rounds]]
+    return {"accum": accum, "accum_sq": accum_sq, "counts": counts, "rounds": res.rounds, "samples": res.samples,
+            "pixels_at_max": res.pixels_at_max, "summary": res.final.as_dict(), "history": history,
+            "stats": st.as_dict()}
 
 
 def write_ppm(path: str, canvas: np.ndarray, nx: int, ny: int) -> None:
