@@ -194,6 +194,30 @@ ADAPTIVE_SIGNATURES = {
     "rtw_scene_query_active": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p]),
 }
 
+
+RTW_FEATURE_CHANNELS = 8  # include/rtw_denoise.h: feature sums per pixel
+
+
+class rtw_denoise_params(C.Structure):
+    """include/rtw_denoise.h"""
+    _fields_ = [("sigma_l", C.c_double), ("sigma_z", C.c_double), ("eps_a", C.c_double), ("iterations", C.c_int32),
+                ("normal_power_log2", C.c_int32)]
+
+
+# the functions of include/rtw_denoise.h (its own header, its own table)
+DENOISE_SIGNATURES = {
+    "rtw_render_features": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera_desc), C.POINTER(rtw_render_params), C.c_void_p,
+                                      C.POINTER(rtw_stats)]),
+    "rtw_scene_query_features": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "rtw_denoise_default_params": (None, [C.POINTER(rtw_denoise_params)]),
+    "rtw_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                              C.POINTER(rtw_denoise_params), C.c_void_p, C.c_void_p]),
+    "rtw_denoise_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_int, C.POINTER(rtw_denoise_params), C.c_void_p, C.c_void_p]),
+    "rtw_finalize_canvas_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "rtw_finalize_canvas_mean_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -214,7 +238,8 @@ def load_library(path) -> C.CDLL:
         raise RuntimeError(f"native library {path} is missing: build it with "
                            f"`python -m raytracingweekend_amd.build` (there is no CPU fallback)")
     L = C.CDLL(str(path))
-    for name, (res, args) in [*SIGNATURES.items(), *NOISE_SIGNATURES.items(), *ADAPTIVE_SIGNATURES.items()]:
+    for name, (res, args) in [*SIGNATURES.items(), *NOISE_SIGNATURES.items(), *ADAPTIVE_SIGNATURES.items(),
+                              *DENOISE_SIGNATURES.items()]:
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

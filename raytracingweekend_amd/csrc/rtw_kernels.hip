@@ -43,6 +43,7 @@
 #include "rtw_fast.h"
 #include "rtw_queue.h"
 #include "host/adaptive.h"
+#include "host/denoise.h"
 #include "host/render_plan.h"
 #include "host/rtw_host_util.h"
 #include "host/scene_layout.h"
@@ -2045,10 +2046,197 @@ __global__ __launch_bounds__(kBlock) void k_select_scatter(select_args A, const 
     }
 }
 
+// ---- rtw_denoise.h ------------------------------------------------------------
+// The filter: host/denoise.h's functions, the host's, one thread per pixel.
+// k_atrous reads the iteration's input image and the read-only features
+// through the caches (a tap: the 64-byte state, the 32-byte geo and the
+// coverage, all 16-byte aligned) and writes the other image of the ping-pong;
+// the 3x3 variance blur is part of the pass (rtw_dn_pass).
+__global__ __launch_bounds__(kBlock) void k_denoise_prepare(const double* __restrict__ accum,
+                                                            const double* __restrict__ accum_sq,
+                                                            const uint32_t* __restrict__ counts, uint32_t n,
+                                                            const double* __restrict__ features, double fs, double eps_a,
+                                                            uint64_t npix, rtw_dn_state* __restrict__ st,
+                                                            rtw_dn_geo* __restrict__ geo, rtw_dn_alb* __restrict__ alb) {
+    const uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x;
+    if (p >= npix) return;
+    const double s1[3] = {accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]};
+    const double s2[3] = {accum_sq[3 * p], accum_sq[3 * p + 1], accum_sq[3 * p + 2]};
+    double f[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = features[8 * p + k];
+    rtw_dn_state s;
+    rtw_dn_geo g;
+    rtw_dn_alb a;
+    rtw_dn_prepare(s1, s2, counts ? counts[p] : n, f, fs, eps_a, s, g, a);
+    st[p] = s, geo[p] = g, alb[p] = a;
+}
+
+__global__ __launch_bounds__(kBlock) void k_atrous(const rtw_dn_state* __restrict__ in,
+                                                   const rtw_dn_geo* __restrict__ geo,
+                                                   const rtw_dn_alb* __restrict__ alb, int nx, int ny, int step,
+                                                   double sigma_l, double sigma_z, int npl2,
+                                                   rtw_dn_state* __restrict__ out) {
+    const uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x;
+    if (p >= (uint64_t)nx * (uint64_t)ny) return;
+    const int j = (int)(p / (uint32_t)nx), i = (int)(p - (uint64_t)j * (uint32_t)nx);
+    out[p] = rtw_dn_pass(rtw_dn_images{in, geo, alb, nx}, nx, ny, i, j, step, sigma_l, sigma_z, npl2);
+}
+
+// ... and with the input staged in LDS, for the dense steps 1 and 2: a
+// workgroup owns a tile of kTileX x kTileY pixels (a wave: two rows of 32) and
+// stages the tile plus a halo of 2 * STEP pixels -- (32 + 4 STEP) x (8 + 4
+// STEP) entries of 104 bytes: 44 928 bytes at step 1, 66 560 at step 2 -- as
+// seven planes: the state's four and the geo's two 16-byte halves and the
+// coverage.  A wave's 32 lanes of a row then read 32 consecutive 16-byte slots
+// of a plane (ds_read_b128 without bank conflicts: each of its 16-lane groups
+// covers all 64 banks once), where the array-of-structs image would put every
+// fourth lane on the same banks.  Entries outside the image are not filled and
+// not read (rtw_dn_pass asks for pixels inside the image only).  The same
+// function on the same values: the bits of k_atrous.
+constexpr int kTileX = 32, kTileY = 8;
+static_assert(kTileX * kTileY == kBlock, "one thread per pixel of the tile");
+constexpr int tile_entries(int step) { return (kTileX + 4 * step) * (kTileY + 4 * step); }
+constexpr size_t tile_bytes(int step) { return (size_t)tile_entries(step) * (sizeof(rtw_dn_state) + sizeof(rtw_dn_geo) + 8); }
+struct dn_tile {
+    const double2* pl;  // planes 0..3 the state, 4..5 the geo, each `n` entries
+    const double* cv;   // the coverage plane
+    int n, pitch, x0, y0;  // entries per plane, entries per row, the image coordinates of entry 0
+    RTW_D int at(int x, int y) const { return (y - y0) * pitch + (x - x0); }
+    RTW_D rtw_dn_state state(int x, int y) const {
+        const int e = at(x, y);
+        const double2 a = pl[e], b = pl[n + e], c = pl[2 * n + e], d = pl[3 * n + e];
+        return rtw_dn_state{{a.x, a.y, b.x}, b.y, {c.x, c.y, d.x}, d.y};
+    }
+    RTW_D double lv(int x, int y) const { return pl[3 * n + at(x, y)].y; }
+    RTW_D rtw_dn_geo geo(int x, int y) const {
+        const int e = at(x, y);
+        const double2 a = pl[4 * n + e], b = pl[5 * n + e];
+        return rtw_dn_geo{{a.x, a.y, b.x}, b.y};
+    }
+    RTW_D double cov(int x, int y) const { return cv[at(x, y)]; }
+};
+template <int STEP>
+__global__ __launch_bounds__(kBlock) void k_atrous_tile(const rtw_dn_state* __restrict__ in,
+                                                        const rtw_dn_geo* __restrict__ geo,
+                                                        const rtw_dn_alb* __restrict__ alb, int nx, int ny,
+                                                        double sigma_l, double sigma_z, int npl2,
+                                                        rtw_dn_state* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char s_tile[];
+    constexpr int H = 2 * STEP, LW = kTileX + 2 * H, LH = kTileY + 2 * H, N = LW * LH;
+    double2* pl = reinterpret_cast<double2*>(s_tile);
+    double* cv = reinterpret_cast<double*>(pl + 6 * N);
+    const int x0 = (int)blockIdx.x * kTileX - H, y0 = (int)blockIdx.y * kTileY - H;
+    for (int e = threadIdx.x; e < N; e += kBlock) {
+        const int ly = e / LW, lx = e - ly * LW;
+        const int x = x0 + lx, y = y0 + ly;
+        if (x < 0 || x >= nx || y < 0 || y >= ny) continue;
+        const size_t q = (size_t)y * (size_t)nx + (size_t)x;
+        const double2* s = reinterpret_cast<const double2*>(in + q);
+        const double2* g = reinterpret_cast<const double2*>(geo + q);
+        pl[e] = s[0], pl[N + e] = s[1], pl[2 * N + e] = s[2], pl[3 * N + e] = s[3];
+        pl[4 * N + e] = g[0], pl[5 * N + e] = g[1];
+        cv[e] = alb[q].cov;
+    }
+    __syncthreads();
+    const int i = (int)blockIdx.x * kTileX + (int)(threadIdx.x % kTileX);
+    const int j = (int)blockIdx.y * kTileY + (int)(threadIdx.x / kTileX);
+    if (i >= nx || j >= ny) return;
+    out[(size_t)j * (size_t)nx + (size_t)i] =
+        rtw_dn_pass(dn_tile{pl, cv, N, LW, x0, y0}, nx, ny, i, j, STEP, sigma_l, sigma_z, npl2);
+}
+
+__global__ __launch_bounds__(kBlock) void k_denoise_finish(const rtw_dn_state* __restrict__ st,
+                                                           const rtw_dn_alb* __restrict__ alb, uint64_t npix,
+                                                           double* __restrict__ out, double* __restrict__ out_var) {
+    const uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x;
+    if (p >= npix) return;
+    double o[3], ov[3];
+    rtw_dn_finish(st[p], alb[p], o, ov);
+    out[3 * p] = o[0], out[3 * p + 1] = o[1], out[3 * p + 2] = o[2];
+    if (out_var) out_var[3 * p] = ov[0], out_var[3 * p + 1] = ov[1], out_var[3 * p + 2] = ov[2];
+}
+
+// iterations == 0: the mean and the variance of the mean, no filter
+__global__ __launch_bounds__(kBlock) void k_denoise_mean(const double* __restrict__ accum,
+                                                         const double* __restrict__ accum_sq,
+                                                         const uint32_t* __restrict__ counts, uint32_t n, uint64_t npix,
+                                                         double* __restrict__ out, double* __restrict__ out_var) {
+    const uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x;
+    if (p >= npix) return;
+    const double s1[3] = {accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]};
+    const double s2[3] = {accum_sq[3 * p], accum_sq[3 * p + 1], accum_sq[3 * p + 2]};
+    double m[3], v[3];
+    const bool ok = rtw_dn_moments(s1, s2, counts ? counts[p] : n, m, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        out[3 * p + c] = m[c];
+        if (out_var) out_var[3 * p + c] = ok ? v[c] : __builtin_nan("");
+    }
+}
+
+// canvas = min(sqrt(mean), 1): k_finalize without the division
+__global__ __launch_bounds__(kBlock) void k_finalize_mean(const double* __restrict__ mean, size_t n,
+                                                          double* __restrict__ canvas) {
+    for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
+        const double s = __builtin_sqrt(mean[k]);
+        canvas[k] = (1.0 < s) ? 1.0 : s;
+    }
+}
+
+// rtw_render_features: the first-hit feature sums of a call's pixels.  A
+// thread owns whole pixels (grid stride over the call's pixels, pixel-major):
+// it loads the pixel's eight sums, replays the pass's camera samples in
+// increasing sample order -- camera_sample is the render's, with the render's
+// pass-local sample id q = sample * npix + pixel -- makes one world query per
+// sample and writes the sums back once, with 16-byte loads and stores.  Not a
+// hot path (one segment per sample): every shading lookup is SF_IMG_ALL's.
+#if !RTW_STRICT_RADIANCE
+template <int F>
+__global__ __launch_bounds__(kBlock) void k_features(scene S, job_t J, double* __restrict__ feat) {
+    for (uint32_t rem = blockIdx.x * kBlock + threadIdx.x; rem < J.npix; rem += gridDim.x * kBlock) {
+        const uint32_t row = udiv_fast(rem, J.div_nx);
+        const uint32_t i = rem - row * (uint32_t)J.nx;
+        const uint32_t j = (uint32_t)J.row_begin + row * (uint32_t)J.row_step;
+        double2* o = reinterpret_cast<double2*>(feat + ((size_t)j * (size_t)J.nx + i) * RTW_FEATURE_CHANNELS);
+        const double2 f0 = o[0], f1 = o[1], f2 = o[2], f3 = o[3];
+        d3 alb{f0.x, f0.y, f1.x}, nrm{f1.y, f2.x, f2.y};
+        double invt = f3.x, cov = f3.y;
+        for (uint32_t sl = 0; sl < J.spp_pass; ++sl) {
+            const uint32_t q = sl * J.npix + rem;
+            uint32_t rng;
+            const ray r = camera_sample<true, false>(J, q, rng);
+            const hit_state h = world_closest<F>(S, r, rng);
+            if (h.prim == -1) {
+                alb = alb + background(S, r.d);
+                continue;
+            }
+            d3 p, n, sfl{0, 0, 0};
+            int mat;
+            bool rect;
+            hit_record<true, false, true>(S, r, h, p, n, mat, rect, sfl);
+            const rtw_material& m = S.materials[mat];
+            d3 a;
+            if (m.type == RTW_MAT_METAL)
+                a = ld3(m.albedo);
+            else if (m.type == RTW_MAT_DIELECTRIC)
+                a = d3{1.0, 1.0, 1.0};
+            else  // lambertian, isotropic: the texture at the hit; a diffuse light: its emit texture
+                a = texture_value<SF_IMG_ALL>(S, m.texture, p, h.prim, sfl);
+            alb = alb + a;
+            nrm = nrm + n;
+            invt = invt + 1.0 / h.t;
+            cov = cov + 1.0;
+        }
+        o[0] = double2{alb.x, alb.y}, o[1] = double2{alb.z, nrm.x}, o[2] = double2{nrm.y, nrm.z}, o[3] = double2{invt, cov};
+    }
+}
+#endif
+
 // ======================================================================
 // host side
 // ======================================================================
-#define HIPCHK(x)                                                                              \
+#define HIPCHK(x)                                                                             \
     do {                                                                                       \
         hipError_t e_ = (x);                                                                   \
         if (e_ != hipSuccess)                                                                  \
@@ -2101,6 +2289,10 @@ struct handle_t {
     dev_buf alist;    // the device copy of a host pixel list; the adaptive loop's list
     dev_buf counts;   // the device copy of a host counts buffer; the adaptive loop's counts
     dev_buf sel;      // rtw_adaptive_select_device: per-block counts, their prefix, the list check's flag
+    // rtw_denoise.h
+    dev_buf features;     // the device copy of a host feature buffer
+    dev_buf dn_state[2];  // rtw_denoise_device: the iteration state, ping-pong (rtw_dn_state)
+    dev_buf dn_geo, dn_alb;  // ... and the per-pixel features the passes only read
     dev_buf ctrs;
     dev_buf camera;                // device copy of the call's camera
     rtw_camera_desc cam_host{};    // its source (lives until the copy ran)
@@ -3404,5 +3596,193 @@ extern "C" int rtw_render_adaptive(void* handle, const rtw_camera_desc* camera, 
     }
     if (out_result) *out_result = res;
     if (out_stats) *out_stats = total;
+    return RTW_OK;
+}
+
+// ======================================================================
+// rtw_denoise.h
+// ======================================================================
+#if !RTW_STRICT_RADIANCE
+namespace {
+// k_features<f> of every entry of kIntersectList: its traversal feature sets
+template <size_t... I>
+std::array<const void*, sizeof...(I)> feature_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_features<kIntersectList[I].f>)...};
+}
+const auto kFeatureRows = feature_rows(std::make_index_sequence<kIntersectList.size()>{});
+}  // namespace
+#endif
+
+// The traversal feature set of the handle's k_features, chosen as the split
+// pair's k_intersect is (rtw_select.h split_resolve).
+static inst features_inst(const handle_t* h) {
+    return split_resolve(inst{h->facts.features & (F_MEDIA | F_WBVH | F_GBVH), SF_IMG_ALL, false}).intersect;
+}
+
+extern "C" int rtw_scene_query_features(void* handle, char name[128]) {
+    const handle_t* h = static_cast<const handle_t*>(handle);
+    if (!h || !name) return rtw_fail(RTW_ERR_INVALID, "rtw_scene_query_features: null argument");
+    if (RTW_STRICT_RADIANCE)
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build has no feature kernel (rtw_render_features)");
+    std::snprintf(name, 128, "%s", kname("k_features", features_inst(h).f, -1).c_str());
+    return RTW_OK;
+}
+
+extern "C" int rtw_render_features(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                                   double* features, rtw_stats* out_stats) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    if (!h || !camera || !prm || !features) return rtw_fail(RTW_ERR_INVALID, "rtw_render_features: null argument");
+#if RTW_STRICT_RADIANCE
+    return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build has no feature kernel (rtw_render_features)");
+#else
+    // the render's plan of the same call: its refusals, sample and row ranges,
+    // passes (pass-local sample ids are 32-bit), camera and job fields.
+    // Precision and depth are not read: planned as one fp64 segment per sample.
+    rtw_render_params R = *prm;
+    R.precision = RTW_PRECISION_FP64, R.max_depth = 1;
+    call_plan P;
+    if (int rc = rtw_plan_call(R, *camera, h->facts, features, nullptr, pass_budget_samples(), 0, &P)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    rtw_stats stats;
+    std::memset(&stats, 0, sizeof stats);
+    if (P.noop) {
+        if (out_stats) *out_stats = stats;
+        return RTW_OK;
+    }
+    const size_t img = (size_t)R.nx * R.ny * RTW_FEATURE_CHANNELS * sizeof(double);
+    hipStream_t st = h->stream;
+    double* f_dev = features;
+    if (R.accum_on_device) {
+        if (int rc = rtw_check_device_ptr(features, h->device, "rtw_render_features")) return rc;
+        if (reinterpret_cast<uintptr_t>(features) % 16)
+            return rtw_fail(RTW_ERR_INVALID, "rtw_render_features: a device feature buffer must be 16-byte aligned");
+    } else {
+        if (int rc = h->features.ensure(img)) return rc;
+        f_dev = static_cast<double*>(h->features.p);
+        HIPCHK(hipMemcpyAsync(f_dev, features, img, hipMemcpyHostToDevice, st));
+    }
+    if (int rc = h->camera.ensure(P.bytes.camera)) return rc;
+    h->cam_host = P.cam_dev;
+    HIPCHK(hipMemcpyAsync(h->camera.p, &h->cam_host, sizeof(rtw_camera_desc), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_recips, dim3(1), dim3(64), 0, st,
+                       reinterpret_cast<double*>(static_cast<char*>(h->camera.p) + sizeof(rtw_camera_desc)), R.nx, R.ny);
+    HIPCHK(hipGetLastError());
+    const int at = index_of(kIntersectList, features_inst(h));
+    if (at < 0) return rtw_fail(RTW_ERR_HIP, "no such instantiation: k_features");
+    hipEvent_t ev_begin = event_at(h, 0), ev_end = event_at(h, 1);
+    if (!ev_begin || !ev_end) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
+    HIPCHK(hipEventRecord(ev_begin, st));
+    job_t J = make_job(h, P, R);
+    J.L = nullptr;
+    const int grid = (int)std::min<uint64_t>((P.npix + kBlock - 1) / kBlock, (uint64_t)h->grid);
+    for (uint64_t done = 0; done < (uint64_t)P.spp_count; done += P.pass_spp) {
+        set_pass(J, rtw_plan_pass(P, R, done));
+        launch(kFeatureRows[at], grid, kBlock, 0, st, h->S, J, f_dev);
+        HIPCHK(hipGetLastError());
+        stats.samples += J.total;
+        stats.launches_intersect++;
+    }
+    HIPCHK(hipEventRecord(ev_end, st));
+    if (!R.accum_on_device) HIPCHK(hipMemcpyAsync(features, f_dev, img, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end));
+    stats.ms_total = ms;
+    stats.segments = stats.samples;
+    stats.bytes_intersect = 68.0 * (double)stats.segments;
+    if (out_stats) *out_stats = stats;
+    return RTW_OK;
+#endif
+}
+
+extern "C" int rtw_denoise_device(void* handle, const double* accum, const double* accum_sq, const uint32_t* counts,
+                                  int n, const double* features, int feature_spp, int nx, int ny,
+                                  const rtw_denoise_params* prm, double* out, double* out_var) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    const char* const what = "rtw_denoise_device";
+    if (!h) return rtw_fail(RTW_ERR_INVALID, "rtw_denoise_device: null scene handle");
+    if (int rc = rtw_denoise_check_args(what, accum, accum_sq, counts, n, features, feature_spp, nx, ny, prm, out, out_var))
+        return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = check_adaptive_ptrs(h, what, {accum, accum_sq, counts, features, out, out_var})) return rc;
+    const uint64_t npix = (uint64_t)nx * (uint64_t)ny;
+    const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock)), block(kBlock);
+    hipStream_t st = h->stream;
+    if (prm->iterations == 0) {
+        hipLaunchKernelGGL(k_denoise_mean, grid, block, 0, st, accum, accum_sq, counts, (uint32_t)n, npix, out, out_var);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        return RTW_OK;
+    }
+    for (dev_buf& b : h->dn_state)
+        if (int rc = b.ensure(npix * sizeof(rtw_dn_state))) return rc;
+    if (int rc = h->dn_geo.ensure(npix * sizeof(rtw_dn_geo))) return rc;
+    if (int rc = h->dn_alb.ensure(npix * sizeof(rtw_dn_alb))) return rc;
+    rtw_dn_state* a = static_cast<rtw_dn_state*>(h->dn_state[0].p);
+    rtw_dn_state* b = static_cast<rtw_dn_state*>(h->dn_state[1].p);
+    rtw_dn_geo* geo = static_cast<rtw_dn_geo*>(h->dn_geo.p);
+    rtw_dn_alb* alb = static_cast<rtw_dn_alb*>(h->dn_alb.p);
+    // Steps 1 and 2 run the LDS-tile form, the sparser steps the global form: measured at 800x800 on one MI355X,
+    // 0.106 against 0.322 ms at step 1 and 0.127 against 0.318 ms at step 2 (profiles/denoise/results.txt); from
+    // step 4 on a tile's halo no longer fits.  RTW_DENOISE_TIMES=1 prints each launch's milliseconds (events around
+    // every launch: how that file was measured).
+    const char* tm = std::getenv("RTW_DENOISE_TIMES");
+    const bool times = tm && *tm && std::atoi(tm) != 0;
+    size_t ev = 0;
+    const auto mark = [&]() -> int {
+        if (!times) return RTW_OK;
+        hipEvent_t e = event_at(h, ev++);
+        if (!e) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
+        HIPCHK(hipEventRecord(e, st));
+        return RTW_OK;
+    };
+    if (int rc = mark()) return rc;
+    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, st, accum, accum_sq, counts, (uint32_t)n, features,
+                       (double)feature_spp, prm->eps_a, npix, a, geo, alb);
+    if (int rc = mark()) return rc;
+    const dim3 tgrid((unsigned)((nx + kTileX - 1) / kTileX), (unsigned)((ny + kTileY - 1) / kTileY));
+    for (int k = 0; k < prm->iterations; ++k) {
+        if (k == 0)
+            hipLaunchKernelGGL(k_atrous_tile<1>, tgrid, block, tile_bytes(1), st, a, geo, alb, nx, ny, prm->sigma_l,
+                               prm->sigma_z, prm->normal_power_log2, b);
+        else if (k == 1)
+            hipLaunchKernelGGL(k_atrous_tile<2>, tgrid, block, tile_bytes(2), st, a, geo, alb, nx, ny, prm->sigma_l,
+                               prm->sigma_z, prm->normal_power_log2, b);
+        else
+            hipLaunchKernelGGL(k_atrous, grid, block, 0, st, a, geo, alb, nx, ny, 1 << k, prm->sigma_l, prm->sigma_z,
+                               prm->normal_power_log2, b);
+        if (int rc = mark()) return rc;
+        std::swap(a, b);
+    }
+    hipLaunchKernelGGL(k_denoise_finish, grid, block, 0, st, a, alb, npix, out, out_var);
+    if (int rc = mark()) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    if (times) {
+        std::fprintf(stderr, "[rtw denoise] %dx%d ms: prepare", nx, ny);
+        float total = 0.f;
+        for (size_t k = 0; k + 1 < ev; ++k) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, h->events[k], h->events[k + 1]));
+            total += ms;
+            if (k == 0) std::fprintf(stderr, " %.4f", ms);
+            else if (k + 2 == ev) std::fprintf(stderr, " finish %.4f", ms);
+            else std::fprintf(stderr, " step%d %.4f", 1 << (k - 1), ms);
+        }
+        std::fprintf(stderr, " total %.4f\n", total);
+    }
+    return RTW_OK;
+}
+
+extern "C" int rtw_finalize_canvas_mean_device(void* handle, const double* mean, int nx, int ny, double* canvas) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    const char* const what = "rtw_finalize_canvas_mean_device";
+    if (!h || !mean || !canvas || nx <= 0 || ny <= 0) return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = check_adaptive_ptrs(h, what, {mean, canvas})) return rc;
+    const size_t n = (size_t)nx * (size_t)ny * 3;
+    hipLaunchKernelGGL(k_finalize_mean, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, mean, n, canvas);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
     return RTW_OK;
 }

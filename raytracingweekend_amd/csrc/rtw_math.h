@@ -72,6 +72,53 @@ RTW_HD double pow5(double x) {
     return x5 + e5;
 }
 
+// x^(2^k) by k squarings (rtw_denoise.h's normal weight: k = 7 is x^128).
+RTW_HD double pow2k(double x, int k) {
+    for (int i = 0; i < k; ++i) x = x * x;
+    return x;
+}
+
+// exp(-x) for x >= 0 (rtw_denoise.h's edge-stopping weight), the same bits on
+// the host and the device: no libm call on either side.  0 above kExpNegCutoff
+// and for a NaN.  The cutoff is 64: exp(-64) = 1.6e-28 is 2^-92, so beside a
+// centre tap of weight 9/64 such a tap is 40 bits below the last bit of a
+// double mean, and a weight's relative sensitivity to its argument, which is
+// the argument itself, stays below 64 (arguments in the hundreds would turn
+// last-bit differences of the variance under the root into visible ones of
+// the weight).  Else
+// -x = n ln2 + r with n = rint(-x / ln2) and ln2 in two parts (fdlibm's
+// ln2HI has 32 significant bits, so n * ln2HI is exact for |n| < 2^20 and so is
+// the first subtraction), |r| <= 0.35; exp(r) by the degree-13 Taylor
+// polynomial in Horner form (truncation 0.35^14 / 14! = 5e-18, rounding a few
+// ulp); 2^n by constructing the exponent bits (n >= -93: normal).  Accurate,
+// not correctly rounded: within 1e-13 relative of exp (tests/cpp/denoise_check.cpp).
+constexpr double kExpNegCutoff = 64.0;
+RTW_HD double exp_neg(double x) {
+    if (!(x <= kExpNegCutoff)) return 0.0;
+    constexpr double inv_ln2 = 1.44269504088896338700e+00;
+    constexpr double ln2_hi = 6.93147180369123816490e-01;  // 0x3FE62E42FEE00000
+    constexpr double ln2_lo = 1.90821492927058770002e-10;
+    const double y = -x;
+    const double n = __builtin_rint(y * inv_ln2);
+    const double r = (y - n * ln2_hi) - n * ln2_lo;
+    double p = 1.0 / 6227020800.0;  // 1 / 13!
+    p = p * r + 1.0 / 479001600.0;
+    p = p * r + 1.0 / 39916800.0;
+    p = p * r + 1.0 / 3628800.0;
+    p = p * r + 1.0 / 362880.0;
+    p = p * r + 1.0 / 40320.0;
+    p = p * r + 1.0 / 5040.0;
+    p = p * r + 1.0 / 720.0;
+    p = p * r + 1.0 / 120.0;
+    p = p * r + 1.0 / 24.0;
+    p = p * r + 1.0 / 6.0;
+    p = p * r + 0.5;
+    p = p * r + 1.0;
+    p = p * r + 1.0;
+    const uint64_t bits = (uint64_t)((int64_t)n + 1023) << 52;
+    return p * __builtin_bit_cast(double, bits);
+}
+
 RTW_HD bool sin_wide_ok(double x) { return __builtin_fabs(x) <= 0x1p19; }
 RTW_HD double sin_wide(double x) {
     double s, c;

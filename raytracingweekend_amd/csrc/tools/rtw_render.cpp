@@ -8,6 +8,7 @@
 //              [--precision fp64|fp32] [--out out.ppm] [--image FILE.ppm]
 //              [--noise] [--noise-target X [--noise-batch 8] [--noise-floor 0.01]]
 //              [--adaptive X [--min-spp 16] [--noise-batch B] [--noise-floor 0.01]]
+//              [--denoise [--denoise-iterations 5]]
 //
 // --noise renders through rtw_render_accumulate_moments (rtw_noise.h) and
 // prints the image-wide noise estimate of the --spp samples.  --noise-target X
@@ -20,6 +21,12 @@
 // many as are done so far) of the pixels whose relative standard error is
 // still above X, with --spp as the most a pixel takes; the canvas divides
 // every pixel's sum by its own sample count.  One GPU only.
+//
+// --denoise filters the image before the canvas step (rtw_denoise.h): the
+// render keeps second moments, rtw_render_features adds the first-hit features
+// of the samples every pixel took, and rtw_denoise (the host function: the
+// device filter's bits) gives the mean the canvas is made of.  With plain,
+// --noise-target and --adaptive renders; one GPU only.
 //
 // --image FILE.ppm (with --scene textured): a P6 or P3 PPM, maxval 255, that
 // replaces the scene's first image texture (rtw_load_ppm).
@@ -42,6 +49,7 @@
 #include "rtw/scene.h"
 #include "rtw_gpu.h"
 #include "rtw_adaptive.h"
+#include "rtw_denoise.h"
 #include "rtw_noise.h"
 
 int main(int argc, char** argv) {
@@ -53,6 +61,8 @@ int main(int argc, char** argv) {
     int noise_batch = 8, min_spp = 16;
     bool adaptive = false, batch_given = false;
     double adaptive_target = 0.0;
+    bool denoise = false;
+    int denoise_iterations = -1;  // (not given: the library's default)
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -79,6 +89,8 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive") adaptive_target = std::atof(next()), adaptive = true;
         else if (a == "--min-spp") min_spp = std::atoi(next());
         else if (a == "--noise-floor") noise_floor = std::atof(next());
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iterations") denoise_iterations = std::atoi(next()), denoise = true;
         else if (a == "--precision") {
             const std::string v = next();
             if (v == "fp64") precision = RTW_PRECISION_FP64;
@@ -111,6 +123,11 @@ int main(int argc, char** argv) {
                      !(noise_floor > 0.0))) {
         std::fprintf(stderr, "--adaptive needs a target >= 0, --min-spp >= 2, --spp >= --min-spp, --noise-batch >= 1, "
                              "--noise-floor > 0\n");
+        return 2;
+    }
+
+    if (denoise && (gpus != 1 || spp < 2 || (denoise_iterations != -1 && (denoise_iterations < 0 || denoise_iterations > 8)))) {
+        std::fprintf(stderr, "--denoise renders on one GPU (--gpus 1) and needs --spp >= 2, --denoise-iterations in [0, 8]\n");
         return 2;
     }
 
@@ -163,9 +180,10 @@ int main(int argc, char** argv) {
     rtw_adaptive_result ar;
     std::memset(&ar, 0, sizeof ar);
     std::vector<uint32_t> counts;
+    std::vector<double> accum_sq;
+    if (adaptive || noise || denoise) accum_sq.assign(accum.size(), 0.0);
     auto t0 = std::chrono::high_resolution_clock::now();
     if (adaptive) {
-        std::vector<double> accum_sq(accum.size(), 0.0);
         counts.assign((size_t)nx * ny, 0u);
         rtw_adaptive_params ap;
         std::memset(&ap, 0, sizeof ap);
@@ -178,7 +196,6 @@ int main(int argc, char** argv) {
     } else if (noise) {
         // one batch of all samples, or (--noise-target) batches that double the
         // total until the estimate reaches the target (render.render_to_noise)
-        std::vector<double> accum_sq(accum.size(), 0.0);
         spp_done = 0;
         while (spp_done < spp) {
             const int want = to_target ? (spp_done == 0 ? noise_batch : spp_done) : spp;
@@ -199,14 +216,35 @@ int main(int argc, char** argv) {
             if (to_target && ns.mean_rel <= noise_target) break;
         }
     } else {
-        const int rc = gpus == 1 ? rtw_render_accumulate(h[0], &cam, &p, accum.data(), &st)
-                                 : rtw_render_multi(gpus, h.data(), &cam, &p, accum.data(), &st);
+        // (--denoise: the same sums, and the second moments beside them)
+        const int rc = denoise     ? rtw_render_accumulate_moments(h[0], &cam, &p, accum.data(), accum_sq.data(), &st)
+                       : gpus == 1 ? rtw_render_accumulate(h[0], &cam, &p, accum.data(), &st)
+                                   : rtw_render_multi(gpus, h.data(), &cam, &p, accum.data(), &st);
         if (rc != RTW_OK) {
             std::fprintf(stderr, "render: %s\n", rtw_last_error());
             return 1;
         }
     }
-    if (adaptive) rtw_finalize_canvas_counts(accum.data(), counts.data(), nx, ny, canvas.data());
+    rtw_denoise_params dp;
+    rtw_denoise_default_params(&dp);
+    double denoise_ms = 0.0;
+    if (denoise) {
+        // the features of the samples every pixel took: all of a plain or
+        // --noise-target render, the first --min-spp of an adaptive one
+        const auto d0 = std::chrono::high_resolution_clock::now();
+        if (denoise_iterations >= 0) dp.iterations = denoise_iterations;
+        const int fspp = adaptive ? min_spp : spp_done;
+        std::vector<double> features((size_t)nx * ny * RTW_FEATURE_CHANNELS, 0.0), mean(accum.size());
+        p.spp_begin = 0, p.spp_count = fspp;
+        if (rtw_render_features(h[0], &cam, &p, features.data(), nullptr) != RTW_OK ||
+            rtw_denoise(accum.data(), accum_sq.data(), adaptive ? counts.data() : nullptr, spp_done, features.data(), fspp,
+                        nx, ny, &dp, mean.data(), nullptr) != RTW_OK ||
+            rtw_finalize_canvas_mean(mean.data(), nx, ny, canvas.data()) != RTW_OK) {
+            std::fprintf(stderr, "denoise: %s\n", rtw_last_error());
+            return 1;
+        }
+        denoise_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - d0).count();
+    } else if (adaptive) rtw_finalize_canvas_counts(accum.data(), counts.data(), nx, ny, canvas.data());
     else rtw_finalize_canvas(accum.data(), nx, ny, spp_done, canvas.data());
     auto t1 = std::chrono::high_resolution_clock::now();
     if (rtw_write_ppm(out.c_str(), canvas.data(), nx, ny) != RTW_OK) {
@@ -227,6 +265,7 @@ int main(int argc, char** argv) {
         std::printf("Adaptive: rounds %u  samples %llu of %llu  mean_rel %.6e  max_rel %.6e  at_max %llu\n", ar.rounds,
                     (unsigned long long)ar.samples, (unsigned long long)nx * ny * spp, ar.final.mean_rel,
                     ar.final.max_rel, (unsigned long long)ar.pixels_at_max);
+    if (denoise) std::printf("Denoise: iterations %d  %.3f ms\n", dp.iterations, denoise_ms);
     for (void* x : h) rtw_scene_free(x);
     if (gpus > 1) rtw_release_communicators();
     rtw_scene_desc_free(desc);

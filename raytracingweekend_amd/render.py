@@ -271,6 +271,87 @@ class DeviceScene:
         check(lib().rtw_scene_query_active(self.handle, _precision(precision), name), "rtw_scene_query_active")
         return name.value.decode()
 
+    # ---- the denoiser (include/rtw_denoise.h) ---------------------------------
+    def _features_ptr(self, features, nx: int, ny: int):
+        """(pointer, on_device) of a feature buffer: float64 of nx*ny*8."""
+        n = nx * ny * _abi.RTW_FEATURE_CHANNELS
+        if isinstance(features, np.ndarray):
+            if features.dtype != np.float64 or features.size != n or not features.flags["C_CONTIGUOUS"]:
+                raise ValueError("features must be a contiguous float64 array of nx*ny*8")
+            return features.ctypes.data_as(C.c_void_p), 0
+        import torch
+        if features.dtype != torch.float64 or features.numel() != n or not features.is_contiguous():
+            raise ValueError("features must be a contiguous float64 tensor of nx*ny*8")
+        if not features.is_cuda or features.device.index != self.device:
+            raise ValueError(f"a torch feature buffer must live on this scene's GPU (cuda:{self.device})")
+        torch.cuda.synchronize(features.device)
+        return C.c_void_p(features.data_ptr()), 1
+
+    def render_features(self, nx: int, ny: int, spp: int, seed: int = 0, *, spp_begin: int = 0, spp_count: int = 0,
+                        row_begin: int = 0, row_step: int = 1, features=None,
+                        camera: Optional[_abi.rtw_camera_desc] = None):
+        """rtw_render_features: ADD the first-hit feature sums (albedo, normal,
+        1/t, coverage: eight per pixel) of the selected samples, the camera
+        rays render_accumulate traces with the same arguments, into `features`
+        (a float64 numpy array of nx*ny*8, or a torch float64 tensor on this
+        device).  Returns (features, stats dict)."""
+        if features is None:
+            features = np.zeros(nx * ny * _abi.RTW_FEATURE_CHANNELS, dtype=np.float64)
+        ptr, on_device = self._features_ptr(features, nx, ny)
+        prm = _abi.rtw_render_params(nx=nx, ny=ny, spp=spp, max_depth=1, seed=seed, spp_begin=spp_begin,
+                                     spp_count=spp_count, row_begin=row_begin, row_step=row_step,
+                                     accum_on_device=on_device, precision=_abi.PRECISIONS["fp64"])
+        st = _abi.rtw_stats()
+        cam = camera if camera is not None else self.scene.camera
+        check(lib().rtw_render_features(self.handle, C.byref(cam), C.byref(prm), ptr, C.byref(st)),
+              "rtw_render_features")
+        return features, st.as_dict()
+
+    def query_features(self) -> str:
+        """rtw_scene_query_features: the kernel render_features launches."""
+        name = C.create_string_buffer(128)
+        check(lib().rtw_scene_query_features(self.handle, name), "rtw_scene_query_features")
+        return name.value.decode()
+
+    def denoise(self, accum, accum_sq, features, nx: int, ny: int, *, n: int = 0, counts=None, feature_spp: int,
+                want_variance: bool = False, **params):
+        """The a-trous filter (rtw_denoise.h) of raw moments with `n` samples
+        per pixel or a per-pixel `counts`.  Torch tensors on this device go
+        through rtw_denoise_device and give tensors; numpy arrays fall through
+        to the host function, render.denoise (the same bits).  `params`:
+        iterations, sigma_l, sigma_z, eps_a, normal_power_log2.  Returns the
+        denoised linear mean, or (mean, variance) with want_variance."""
+        if isinstance(accum, np.ndarray):
+            return denoise(accum, accum_sq, features, nx, ny, n=n, counts=counts, feature_spp=feature_spp,
+                           want_variance=want_variance, **params)
+        import torch
+        ptr, ptr_sq, _ = self._moment_buffers(accum, accum_sq, nx, ny)
+        ptr_f, on_device = self._features_ptr(features, nx, ny)
+        if not on_device:
+            raise ValueError("features must be a torch tensor on this device, like the moments")
+        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", True) if counts is not None else None
+        out = torch.empty_like(accum)
+        var = torch.empty_like(accum) if want_variance else None
+        torch.cuda.synchronize(accum.device)
+        prm = denoise_params(**params)
+        check(lib().rtw_denoise_device(self.handle, ptr, ptr_sq, ptr_counts, n, ptr_f, feature_spp, nx, ny,
+                                       C.byref(prm), C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(var.data_ptr()) if want_variance else None), "rtw_denoise_device")
+        return (out, var) if want_variance else out
+
+    def finalize_mean(self, mean, nx: int, ny: int):
+        """canvas = min(sqrt(mean), 1) of a denoised mean
+        (rtw_finalize_canvas_mean[_device])."""
+        if isinstance(mean, np.ndarray):
+            return finalize_mean(mean, nx, ny)
+        import torch
+        ptr, _ = self._accum_ptr(mean, nx, ny, "mean")
+        canvas = torch.empty_like(mean)
+        torch.cuda.synchronize(mean.device)
+        check(lib().rtw_finalize_canvas_mean_device(self.handle, ptr, nx, ny, C.c_void_p(canvas.data_ptr())),
+              "rtw_finalize_canvas_mean_device")
+        return canvas
+
     def finalize_device(self, accum, nx: int, ny: int, spp: int, canvas=None):
         """canvas = min(sqrt(accum / spp), 1) on the GPU (torch float64 CUDA
         tensors of nx*ny*3 on this device).  Returns the canvas tensor."""
@@ -531,7 +612,8 @@ def adaptive_schedule(min_spp: int, max_spp: int, batch: int = 0):
 
 def render_adaptive(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: int = 0, *, target_rel: float,
                     min_spp: int = 16, batch: int = 0, floor: float = 1e-2, precision: str = "fp64",
-                    device_buffers: bool = False, camera=None) -> dict:
+                    device_buffers: bool = False, camera=None, denoise: bool = False,
+                    denoise_args: Optional[dict] = None) -> dict:
     """Adaptive per-pixel sampling, the library's loop (rtw_render_adaptive):
     [0, min_spp) of every pixel, then rounds of `batch` samples (0: doubling)
     of the pixels whose relative standard error is still above target_rel,
@@ -542,7 +624,13 @@ def render_adaptive(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: in
     Returns a dict: accum, accum_sq (float64), counts (uint32 array, or int32
     tensor with device_buffers), rounds, samples, pixels_at_max, summary
     (noise_estimate_counts of the result), history (per round: (begin, count,
-    pixels rendered), read from the schedule and the counts) and stats."""
+    pixels rendered), read from the schedule and the counts) and stats.
+
+    denoise=True additionally renders the first-hit features of the samples
+    [0, min_spp) every pixel took and filters the moments with the per-pixel
+    counts (ds.denoise, rtw_denoise.h; denoise_args: its parameters): the
+    dict gains features, feature_spp and denoised (the linear mean; finalize
+    it with ds.finalize_mean)."""
     ap = _adaptive_params(target_rel, floor, min_spp, max_spp, batch)
     if device_buffers:
         import torch
@@ -564,9 +652,94 @@ def render_adaptive(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: in
                                     C.byref(st)), "rtw_render_adaptive")
     c_host = counts if isinstance(counts, np.ndarray) else counts.cpu().numpy()
     history = [(b, c, int((c_host > b).sum())) for b, c in adaptive_schedule(min_spp, max_spp, batch)[:res.rounds]]
-    return {"accum": accum, "accum_sq": accum_sq, "counts": counts, "rounds": res.rounds, "samples": res.samples,
-            "pixels_at_max": res.pixels_at_max, "summary": res.final.as_dict(), "history": history,
-            "stats": st.as_dict()}
+    out = {"accum": accum, "accum_sq": accum_sq, "counts": counts, "rounds": res.rounds, "samples": res.samples,
+           "pixels_at_max": res.pixels_at_max, "summary": res.final.as_dict(), "history": history,
+           "stats": st.as_dict()}
+    if denoise:
+        features = _feature_zeros(nx, ny, ds.device if device_buffers else None)
+        ds.render_features(nx, ny, max_spp, seed, spp_begin=0, spp_count=min_spp, features=features, camera=camera)
+        out["features"], out["feature_spp"] = features, min_spp
+        out["denoised"] = ds.denoise(accum, accum_sq, features, nx, ny, counts=counts, feature_spp=min_spp,
+                                     **(denoise_args or {}))
+    return out
+
+
+def _feature_zeros(nx: int, ny: int, device: Optional[int]):
+    n = nx * ny * _abi.RTW_FEATURE_CHANNELS
+    if device is None:
+        return np.zeros(n, dtype=np.float64)
+    import torch
+    return torch.zeros(n, dtype=torch.float64, device=f"cuda:{device}")
+
+
+def denoise_params(**params) -> _abi.rtw_denoise_params:
+    """rtw_denoise_default_params with `params` (iterations, sigma_l, sigma_z,
+    eps_a, normal_power_log2) written over the defaults."""
+    prm = _abi.rtw_denoise_params()
+    lib().rtw_denoise_default_params(C.byref(prm))
+    for k, v in params.items():
+        if k not in ("iterations", "sigma_l", "sigma_z", "eps_a", "normal_power_log2"):
+            raise ValueError(f"unknown denoise parameter {k!r}")
+        setattr(prm, k, v)
+    return prm
+
+
+def denoise(accum, accum_sq, features, nx: int, ny: int, *, n: int = 0, counts=None, feature_spp: int,
+            want_variance: bool = False, **params):
+    """rtw_denoise on the host: the variance-guided edge-avoiding a-trous
+    filter (include/rtw_denoise.h) of the raw moments of `n` samples per pixel
+    (or a uint32 `counts` per pixel) guided by the first-hit feature sums of
+    `feature_spp` samples per pixel (DeviceScene.render_features).  Returns
+    the denoised linear mean (nx*ny*3), or (mean, variance) with
+    want_variance."""
+    a = np.ascontiguousarray(accum, dtype=np.float64)
+    q = np.ascontiguousarray(accum_sq, dtype=np.float64)
+    f = np.ascontiguousarray(features, dtype=np.float64)
+    c = np.ascontiguousarray(counts, dtype=np.uint32) if counts is not None else None
+    if a.size != nx * ny * 3 or q.size != nx * ny * 3 or f.size != nx * ny * _abi.RTW_FEATURE_CHANNELS \
+            or (c is not None and c.size != nx * ny):
+        raise ValueError("the moments must hold nx*ny*3 values, the features nx*ny*8 and counts nx*ny")
+    out = np.empty(nx * ny * 3, dtype=np.float64)
+    var = np.empty(nx * ny * 3, dtype=np.float64) if want_variance else None
+    prm = denoise_params(**params)
+    check(lib().rtw_denoise(a.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p),
+                            c.ctypes.data_as(C.c_void_p) if c is not None else None, n,
+                            f.ctypes.data_as(C.c_void_p), feature_spp, nx, ny, C.byref(prm),
+                            out.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p) if want_variance else None),
+          "rtw_denoise")
+    return (out, var) if want_variance else out
+
+
+def finalize_mean(mean, nx: int, ny: int) -> np.ndarray:
+    """canvas = min(sqrt(mean), 1) via rtw_finalize_canvas_mean."""
+    m = np.ascontiguousarray(mean, dtype=np.float64)
+    if m.size != nx * ny * 3:
+        raise ValueError("mean must hold nx*ny*3 values")
+    out = np.empty(nx * ny * 3, dtype=np.float64)
+    check(lib().rtw_finalize_canvas_mean(m.ctypes.data_as(C.c_void_p), nx, ny, out.ctypes.data_as(C.c_void_p)),
+          "rtw_finalize_canvas_mean")
+    return out
+
+
+def render_denoised(ds, nx: int, ny: int, spp: int, max_depth: int, seed: int = 0, *, precision: str = "fp64",
+                    device_buffers: bool = False, camera=None, **params) -> dict:
+    """Render `spp` samples' moments and first-hit features, then filter
+    (rtw_denoise.h).  Returns a dict: accum, accum_sq, features, denoised (the
+    linear mean), canvas (min(sqrt(denoised), 1)) and stats (of the render)."""
+    if spp < 2:
+        raise ValueError("spp must be at least 2 (a variance needs two samples)")
+    accum = accum_sq = None
+    if device_buffers:
+        import torch
+        accum = torch.zeros(nx * ny * 3, dtype=torch.float64, device=f"cuda:{ds.device}")
+        accum_sq = torch.zeros_like(accum)
+    accum, accum_sq, stats = ds.render_moments(nx, ny, spp, max_depth, seed, accum=accum, accum_sq=accum_sq,
+                                               camera=camera, precision=precision)
+    features = _feature_zeros(nx, ny, ds.device if device_buffers else None)
+    ds.render_features(nx, ny, spp, seed, features=features, camera=camera)
+    den = ds.denoise(accum, accum_sq, features, nx, ny, n=spp, feature_spp=spp, **params)
+    return {"accum": accum, "accum_sq": accum_sq, "features": features, "denoised": den,
+            "canvas": ds.finalize_mean(den, nx, ny), "stats": stats}
 
 
 def write_ppm(path: str, canvas: np.ndarray, nx: int, ny: int) -> None:
