@@ -1,11 +1,9 @@
 // adaptive.cpp — host side of rtw_adaptive.h: the active-pixel select, the
 // noise estimate and the canvas with per-pixel counts, the argument checks and
 // the adaptive loop's schedule (the device versions of the first three, the
-// same arithmetic per pixel through adaptive.h, and the loop itself are in
+// same arithmetic per pixel through moments.h, and the loop itself are in
 // rtw_kernels.hip).  Plain C++, no HIP.
 #include "adaptive.h"
-#include <cmath>
-#include <limits>
 #include <string>
 #include "rtw_host_util.h"
 
@@ -86,9 +84,10 @@ extern "C" int rtw_adaptive_select(const double* accum, const double* accum_sq, 
         return rc;
     const size_t npix = (size_t)nx * (size_t)ny;
     const double floor3 = 3.0 * floor;
+    const rtw_count_src cnt{counts, 0};
     uint64_t n = 0;
     for (size_t p = 0; p < npix; ++p)
-        if (rtw_pixel_active(accum + 3 * p, accum_sq + 3 * p, counts[p], floor3, target_rel, max_count))
+        if (rtw_pixel_active(accum + 3 * p, accum_sq + 3 * p, cnt[p], floor3, target_rel, max_count))
             active_out[n++] = (uint32_t)p;
     *n_active_out = n;
     return RTW_OK;
@@ -99,43 +98,14 @@ extern "C" int rtw_noise_estimate_counts(const double* accum, const double* accu
     if (int rc = rtw_adaptive_check_estimate("rtw_noise_estimate_counts", accum, accum_sq, counts, nx, ny, floor,
                                              stderr_rgb))
         return rc;
-    const size_t npix = (size_t)nx * (size_t)ny;
-    const double floor3 = 3.0 * floor;
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    uint64_t pixels = 0, nonfinite = 0;
-    double sum_rel = 0.0, max_rel = -std::numeric_limits<double>::infinity(), sum_se2 = 0.0;
-    for (size_t p = 0; p < npix; ++p) {
-        double se[3];
-        bool finite = false;
-        double rel = 0.0;
-        if (counts[p] >= 2)
-            rel = rtw_pixel_rel(accum + 3 * p, accum_sq + 3 * p, (double)counts[p], (double)(counts[p] - 1), floor3, se,
-                                &finite);
-        if (!finite) {
-            ++nonfinite;
-            if (stderr_rgb) stderr_rgb[3 * p] = stderr_rgb[3 * p + 1] = stderr_rgb[3 * p + 2] = nan;
-            continue;
-        }
-        if (stderr_rgb) stderr_rgb[3 * p] = se[0], stderr_rgb[3 * p + 1] = se[1], stderr_rgb[3 * p + 2] = se[2];
-        ++pixels;
-        sum_rel = sum_rel + rel;
-        if (rel > max_rel) max_rel = rel;
-        sum_se2 = sum_se2 + ((se[0] * se[0] + se[1] * se[1]) + se[2] * se[2]);
-    }
-    if (out) rtw_noise_finish(pixels, nonfinite, sum_rel, max_rel, sum_se2, out);
+    rtw_noise_estimate_pixels(accum, accum_sq, rtw_count_src{counts, 0}, (size_t)nx * (size_t)ny, floor, stderr_rgb,
+                              out);
     return RTW_OK;
 }
 
 extern "C" int rtw_finalize_canvas_counts(const double* accum, const uint32_t* counts, int nx, int ny, double* canvas) {
     if (!accum || !counts || !canvas || nx <= 0 || ny <= 0)
         return rtw_fail(RTW_ERR_INVALID, "rtw_finalize_canvas_counts: bad argument");
-    const size_t npix = (size_t)nx * (size_t)ny;
-    for (size_t p = 0; p < npix; ++p) {
-        const double d = static_cast<double>(counts[p]);
-        for (int c = 0; c < 3; ++c) {
-            const double s = std::sqrt(accum[3 * p + c] / d);
-            canvas[3 * p + c] = (1.0 < s) ? 1.0 : s;
-        }
-    }
+    rtw_canvas_fill(accum, (size_t)nx * (size_t)ny * 3, rtw_div_counts{counts}, canvas);
     return RTW_OK;
 }

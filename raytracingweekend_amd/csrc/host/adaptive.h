@@ -1,32 +1,12 @@
 // adaptive.h — what the host and the device halves of rtw_adaptive.h share:
-// rtw_noise.h's per-pixel expression with the pixel's own sample count, the
-// active-pixel predicate, the adaptive loop's schedule and the argument
-// checks.  The per-pixel functions compile for both sides (RTW_HD, rtw_div.h),
-// so adaptive.cpp's loops and the kernels of rtw_kernels.hip evaluate the same
-// operations in the same order (the library builds with -ffp-contract=off).
+// the active-pixel predicate (over moments.h's per-pixel expression, compiled
+// for both sides like it), the adaptive loop's schedule and the argument
+// checks.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include "moments.h"
 #include "rtw_adaptive.h"
-#include "rtw_div.h"
-
-// rtw_noise.h's expression for one pixel: s1 / s2 its three raw first / second
-// moments, n its sample count as a double (dn1 = n - 1).  Fills se[3] and
-// returns rel_p; *finite: the six moments are finite.
-RTW_HD double rtw_pixel_rel(const double* s1, const double* s2, double dn, double dn1, double floor3, double* se,
-                            bool* finite) {
-    double m[3];
-    bool fin = true;
-    for (int c = 0; c < 3; ++c) {
-        fin = fin && __builtin_isfinite(s1[c]) && __builtin_isfinite(s2[c]);
-        m[c] = s1[c] / dn;
-        double v = (s2[c] - s1[c] * m[c]) / dn1;
-        if (v < 0.0) v = 0.0;
-        se[c] = __builtin_sqrt(v / dn);
-    }
-    *finite = fin;
-    return ((se[0] + se[1]) + se[2]) / (((m[0] + m[1]) + m[2]) + floor3);
-}
 
 // Whether a pixel still takes samples: fewer than max_count so far, finite
 // moments, and either too few samples for a variance or rel_p > target_rel.
@@ -38,7 +18,7 @@ RTW_HD bool rtw_pixel_active(const double* s1, const double* s2, uint32_t count,
     if (!finite) return false;
     if (count < 2) return true;
     double se[3];
-    const double rel = rtw_pixel_rel(s1, s2, (double)count, (double)(count - 1), floor3, se, &finite);
+    const double rel = rtw_pixel_rel(s1, s2, count, floor3, se, &finite);
     return rel > target_rel;
 }
 

@@ -1,7 +1,7 @@
 // denoise.cpp — host side of rtw_denoise.h: the filter on host buffers, the
 // canvas step of its output and the argument checks (the device version, the
-// same arithmetic per pixel through denoise.h, and the feature render are in
-// rtw_kernels.hip).  Plain C++, no HIP.
+// same arithmetic per pixel through denoise.h and moments.h, and the feature
+// render are in rtw_kernels.hip).  Plain C++, no HIP.
 #include "denoise.h"
 #include <cmath>
 #include <string>
@@ -54,10 +54,11 @@ extern "C" int rtw_denoise(const double* accum, const double* accum_sq, const ui
                                         out_var))
         return rc;
     const size_t npix = (size_t)nx * (size_t)ny;
+    const rtw_count_src cnt{counts, (uint32_t)n};
     if (prm->iterations == 0) {
         for (size_t p = 0; p < npix; ++p) {
             double m[3], v[3];
-            const bool ok = rtw_dn_moments(accum + 3 * p, accum_sq + 3 * p, counts ? counts[p] : (uint32_t)n, m, v);
+            const bool ok = rtw_pixel_moments(accum + 3 * p, accum_sq + 3 * p, cnt[p], m, v);
             for (int c = 0; c < 3; ++c) {
                 out[3 * p + c] = m[c];
                 if (out_var) out_var[3 * p + c] = ok ? v[c] : std::nan("");
@@ -70,8 +71,7 @@ extern "C" int rtw_denoise(const double* accum, const double* accum_sq, const ui
     std::vector<rtw_dn_alb> alb(npix);
     const double fs = (double)feature_spp;
     for (size_t p = 0; p < npix; ++p)
-        rtw_dn_prepare(accum + 3 * p, accum_sq + 3 * p, counts ? counts[p] : (uint32_t)n, features + 8 * p, fs, prm->eps_a,
-                       a[p], geo[p], alb[p]);
+        rtw_dn_prepare(accum + 3 * p, accum_sq + 3 * p, cnt[p], features + 8 * p, fs, prm->eps_a, a[p], geo[p], alb[p]);
     for (int k = 0; k < prm->iterations; ++k) {
         const rtw_dn_images img{a.data(), geo.data(), alb.data(), nx};
         for (int j = 0; j < ny; ++j)
@@ -86,10 +86,6 @@ extern "C" int rtw_denoise(const double* accum, const double* accum_sq, const ui
 
 extern "C" int rtw_finalize_canvas_mean(const double* mean, int nx, int ny, double* canvas) {
     if (!mean || !canvas || nx <= 0 || ny <= 0) return rtw_fail(RTW_ERR_INVALID, "rtw_finalize_canvas_mean: bad argument");
-    const size_t n = (size_t)nx * (size_t)ny * 3;
-    for (size_t k = 0; k < n; ++k) {
-        const double s = std::sqrt(mean[k]);
-        canvas[k] = (1.0 < s) ? 1.0 : s;
-    }
+    rtw_canvas_fill(mean, (size_t)nx * (size_t)ny * 3, rtw_div_none{}, canvas);
     return RTW_OK;
 }

@@ -1,11 +1,13 @@
 // denoise.h — what the host and the device halves of rtw_denoise.h share: the
-// filter's per-pixel and per-tap arithmetic and the argument checks.  The
+// filter's per-pixel and per-tap arithmetic (a pixel's mean and the variance
+// of its mean: moments.h's rtw_pixel_moments) and the argument checks.  The
 // functions compile for both sides (RTW_HD), so denoise.cpp's loops and the
 // kernels of rtw_kernels.hip evaluate the operations rtw_denoise.h states, in
 // its order (the library builds with -ffp-contract=off).
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include "moments.h"
 #include "rtw_denoise.h"
 #include "rtw_math.h"
 
@@ -24,21 +26,6 @@ struct alignas(16) rtw_dn_alb {
 };
 static_assert(sizeof(rtw_dn_state) == 64 && sizeof(rtw_dn_geo) == 32 && sizeof(rtw_dn_alb) == 32, "packed for 16-byte loads");
 
-// m and the variance of the mean of one pixel (rtw_noise.h's expression);
-// returns whether n >= 2 and the six moments are finite.
-RTW_HD bool rtw_dn_moments(const double* s1, const double* s2, uint32_t n, double* m, double* v) {
-    const double dn = (double)n, dn1 = (double)n - 1.0;
-    bool fin = n >= 2;
-    for (int c = 0; c < 3; ++c) {
-        fin = fin && __builtin_isfinite(s1[c]) && __builtin_isfinite(s2[c]);
-        m[c] = n ? s1[c] / dn : __builtin_nan("");
-        double x = (s2[c] - s1[c] * m[c]) / dn1;
-        if (x < 0.0) x = 0.0;
-        v[c] = x / dn;
-    }
-    return fin;
-}
-
 RTW_HD void rtw_dn_set_l(rtw_dn_state& s) {
     s.l = ((s.c[0] + s.c[1]) + s.c[2]) / 3.0;
     s.lv = ((s.v[0] + s.v[1]) + s.v[2]) / 9.0;
@@ -48,7 +35,7 @@ RTW_HD void rtw_dn_set_l(rtw_dn_state& s) {
 RTW_HD void rtw_dn_prepare(const double* s1, const double* s2, uint32_t n, const double* f, double fs, double eps_a,
                            rtw_dn_state& st, rtw_dn_geo& g, rtw_dn_alb& al) {
     double m[3], v[3];
-    bool ok = rtw_dn_moments(s1, s2, n, m, v);
+    bool ok = rtw_pixel_moments(s1, s2, n, m, v);  // (moments.h: n < 2 is not ok, n == 0 a NaN mean)
     for (int k = 0; k < 8; ++k) ok = ok && __builtin_isfinite(f[k]);
     for (int c = 0; c < 3; ++c) {
         al.a[c] = f[c] / fs + eps_a;

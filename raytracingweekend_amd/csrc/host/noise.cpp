@@ -1,10 +1,11 @@
 // noise.cpp — host side of rtw_noise.h: the standard-error map of a render's
-// raw moments and its image-wide summary (the device version, the same
-// arithmetic per pixel, is k_noise_pixels in rtw_kernels.hip).
+// raw moments and its image-wide summary, with one sample count or each
+// pixel's own (the per-pixel arithmetic is moments.h's, which k_noise_pixels
+// in rtw_kernels.hip runs too).
 #include <cmath>
 #include <cstdint>
-#include <limits>
 #include <string>
+#include "moments.h"
 #include "rtw_host_util.h"
 #include "rtw_noise.h"
 
@@ -29,46 +30,26 @@ int rtw_noise_check_args(const char* what, const void* accum, const void* accum_
     return RTW_OK;
 }
 
-void rtw_noise_finish(uint64_t pixels, uint64_t nonfinite, double sum_rel, double max_rel, double sum_se2,
-                      rtw_noise_summary* out) {
-    out->pixels = pixels;
-    out->nonfinite = nonfinite;
-    out->mean_rel = pixels ? sum_rel / (double)pixels : 0.0;
-    out->max_rel = pixels ? max_rel : 0.0;
-    out->rms_stderr = pixels ? std::sqrt(sum_se2 / ((double)pixels * 3.0)) : 0.0;
+void rtw_noise_finish(const rtw_noise_acc& t, rtw_noise_summary* out) {
+    out->pixels = t.pixels;
+    out->nonfinite = t.nonfinite;
+    out->mean_rel = t.pixels ? t.sum_rel / (double)t.pixels : 0.0;
+    out->max_rel = t.pixels ? t.max_rel : 0.0;
+    out->rms_stderr = t.pixels ? std::sqrt(t.sum_se2 / ((double)t.pixels * 3.0)) : 0.0;
+}
+
+void rtw_noise_estimate_pixels(const double* accum, const double* accum_sq, const rtw_count_src& cnt, size_t npix,
+                               double floor, double* stderr_rgb, rtw_noise_summary* out) {
+    const double floor3 = 3.0 * floor;
+    rtw_noise_acc t = rtw_noise_acc::empty();
+    for (size_t p = 0; p < npix; ++p) t.add_pixel(accum, accum_sq, cnt, p, floor3, stderr_rgb);
+    if (out) rtw_noise_finish(t, out);
 }
 
 extern "C" int rtw_noise_estimate(const double* accum, const double* accum_sq, int nx, int ny, int n, double floor,
                                   double* stderr_rgb, rtw_noise_summary* out) {
     if (int rc = rtw_noise_check_args("rtw_noise_estimate", accum, accum_sq, nx, ny, n, floor, stderr_rgb)) return rc;
-    const size_t npix = (size_t)nx * (size_t)ny;
-    const double dn = (double)n, dn1 = (double)(n - 1), floor3 = 3.0 * floor;
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    uint64_t pixels = 0, nonfinite = 0;
-    double sum_rel = 0.0, max_rel = -std::numeric_limits<double>::infinity(), sum_se2 = 0.0;
-    for (size_t p = 0; p < npix; ++p) {
-        double se[3], m[3];
-        bool finite = true;
-        for (int c = 0; c < 3; ++c) {
-            const double s1 = accum[3 * p + c], s2 = accum_sq[3 * p + c];
-            finite = finite && std::isfinite(s1) && std::isfinite(s2);
-            m[c] = s1 / dn;
-            double v = (s2 - s1 * m[c]) / dn1;
-            if (v < 0.0) v = 0.0;
-            se[c] = std::sqrt(v / dn);
-        }
-        if (!finite) {
-            ++nonfinite;
-            if (stderr_rgb) stderr_rgb[3 * p] = stderr_rgb[3 * p + 1] = stderr_rgb[3 * p + 2] = nan;
-            continue;
-        }
-        if (stderr_rgb) stderr_rgb[3 * p] = se[0], stderr_rgb[3 * p + 1] = se[1], stderr_rgb[3 * p + 2] = se[2];
-        const double rel = ((se[0] + se[1]) + se[2]) / (((m[0] + m[1]) + m[2]) + floor3);
-        ++pixels;
-        sum_rel = sum_rel + rel;
-        if (rel > max_rel) max_rel = rel;
-        sum_se2 = sum_se2 + ((se[0] * se[0] + se[1] * se[1]) + se[2] * se[2]);
-    }
-    if (out) rtw_noise_finish(pixels, nonfinite, sum_rel, max_rel, sum_se2, out);
+    rtw_noise_estimate_pixels(accum, accum_sq, rtw_count_src{nullptr, (uint32_t)n}, (size_t)nx * (size_t)ny, floor,
+                              stderr_rgb, out);
     return RTW_OK;
 }

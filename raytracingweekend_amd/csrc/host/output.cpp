@@ -1,7 +1,7 @@
 // output.cpp — canvas finalisation, PPM writer, error state, seeding.
-#include <cmath>
 #include <cstdio>
 #include <string>
+#include "moments.h"
 #include "rtw_host_util.h"
 
 namespace {
@@ -18,15 +18,9 @@ extern "C" const char* rtw_last_error(void) { return g_last_error.c_str(); }
 extern "C" int rtw_abi_version(void) { return RTW_ABI_VERSION; }
 
 // RayTracingWeekend.cpp:241-244: col = sum / spp (a true division, the double
-// broadcast to vec3), then std::min(sqrt(c), 1.0) — std::min returns its
-// first argument unless the second compares smaller, so a NaN passes through.
+// broadcast to vec3), then std::min(sqrt(c), 1.0): moments.h's canvas value.
 extern "C" void rtw_finalize_canvas(const double* accum, int nx, int ny, int spp, double* canvas) {
-    const size_t n = (size_t)nx * (size_t)ny * 3;
-    const double d = static_cast<double>(spp);
-    for (size_t k = 0; k < n; ++k) {
-        const double s = std::sqrt(accum[k] / d);
-        canvas[k] = (1.0 < s) ? 1.0 : s;
-    }
+    rtw_canvas_fill(accum, (size_t)nx * (size_t)ny * 3, rtw_div_uniform{static_cast<double>(spp)}, canvas);
 }
 
 // RayTracingWeekend.cpp:252-276: ASCII P3, rows written top (j = ny-1) to

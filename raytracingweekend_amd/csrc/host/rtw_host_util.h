@@ -38,7 +38,7 @@ int rtw_check_device_ptr(const void* p, int device, const char* what, bool allow
 
 // rtw_noise.h's shared pieces (noise.cpp), used by the device estimator too:
 // the argument checks of rtw_noise_estimate[_device], whether two buffers of
-// `bytes` bytes share a byte, and the summary from the image-wide sums.
+// `bytes` bytes share a byte (the estimator's loop and summary: moments.h).
 bool rtw_ranges_overlap(const void* a, const void* b, size_t bytes);
 // ... and of two buffers of different sizes: [a, a+na) and [b, b+nb) share a byte
 inline bool rtw_spans_overlap(const void* a, size_t na, const void* b, size_t nb) {
@@ -47,5 +47,3 @@ inline bool rtw_spans_overlap(const void* a, size_t na, const void* b, size_t nb
 }
 int rtw_noise_check_args(const char* what, const void* accum, const void* accum_sq, int nx, int ny, int n,
                          double floor, const void* stderr_rgb);
-void rtw_noise_finish(uint64_t pixels, uint64_t nonfinite, double sum_rel, double max_rel, double sum_se2,
-                      rtw_noise_summary* out);

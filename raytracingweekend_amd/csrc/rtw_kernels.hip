@@ -1827,147 +1827,56 @@ __global__ __launch_bounds__(kBlock) void k_set_counts(uint32_t* __restrict__ co
     for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) counts[k] = v;
 }
 
-// canvas = min(sqrt(accum / spp), 1) (RayTracingWeekend.cpp:241-244)
-__global__ __launch_bounds__(kBlock) void k_finalize(const double* __restrict__ accum, size_t n, double spp,
+// canvas = min(sqrt(accum / spp), 1) (RayTracingWeekend.cpp:241-244), one
+// body for moments.h's divisor sources: D = rtw_div_uniform is the render's
+// finalize, rtw_div_counts divides by each pixel's own sample count,
+// rtw_div_none takes a mean as it is.  (A template parameter: the uniform
+// form has no load or branch for the other two.)
+template <class D>
+__global__ __launch_bounds__(kBlock) void k_finalize(const double* __restrict__ accum, size_t n, D div,
                                                      double* __restrict__ canvas) {
-    for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
-        const double s = __builtin_sqrt(accum[k] / spp);
-        canvas[k] = (1.0 < s) ? 1.0 : s;
-    }
-}
-
-// ... with each pixel's own sample count (rtw_finalize_canvas_counts)
-__global__ __launch_bounds__(kBlock) void k_finalize_counts(const double* __restrict__ accum,
-                                                            const uint32_t* __restrict__ counts, size_t n,
-                                                            double* __restrict__ canvas) {
-    for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
-        const double s = __builtin_sqrt(accum[k] / (double)counts[k / 3]);
-        canvas[k] = (1.0 < s) ? 1.0 : s;
-    }
+    for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock)
+        canvas[k] = rtw_canvas_value(div(accum[k], k));
 }
 
 // rtw_noise.h on the device: the standard error of every channel from the
-// raw moments (the operations of rtw_noise_estimate, noise.cpp, in the same
-// order: the map is bit-identical) and one partial of the image-wide summary
-// per block.  Deterministic: a thread takes pixels p, p + grid*kBlock, ... in
-// order, a wave folds its lanes with a fixed shuffle tree, thread 0 adds the
-// waves' values from LDS in wave order, the host adds the blocks' partials in
+// raw moments (moments.h's add_pixel, the host loop's: the map is
+// bit-identical) and one partial of the image-wide summary per block; cnt is
+// one n for every pixel or each pixel's own counts[p] (rtw_adaptive.h: a pixel
+// with fewer than two samples is left out as a non-finite one is).
+// Deterministic: a thread takes pixels p, p + grid*kBlock, ... in order, a
+// wave folds its lanes with a fixed shuffle tree, thread 0 merges the waves'
+// values from LDS in wave order, the host merges the blocks' partials in
 // block order; the grid (noise_grid) depends on the pixel count only.  No
 // atomics: the two counters travel in the partials as well.
-struct noise_part {
-    double sum_rel, max_rel, sum_se2;
-    unsigned long long pixels, nonfinite;
-};
 constexpr unsigned kNoiseMaxGrid = 1024;
 unsigned noise_grid(uint64_t npix) {
     return (unsigned)std::min<uint64_t>((npix + kBlock - 1) / kBlock, kNoiseMaxGrid);
 }
 
-// A block's partial of the summary from its threads' (k_noise_pixels' fold:
-// a fixed shuffle tree per wave, then thread 0 over the waves in wave order).
-// Every thread of the block calls it.
-__device__ __forceinline__ void noise_fold(noise_part a, noise_part* s_part, noise_part* __restrict__ parts) {
+__global__ __launch_bounds__(kBlock) void k_noise_pixels(const double* __restrict__ accum,
+                                                         const double* __restrict__ accum_sq, rtw_count_src cnt,
+                                                         uint64_t npix, double floor3,
+                                                         double* __restrict__ stderr_rgb,
+                                                         rtw_noise_acc* __restrict__ parts) {
+    __shared__ rtw_noise_acc s_part[kWaves];
+    rtw_noise_acc a = rtw_noise_acc::empty();
+    // (64-bit p: the stride may carry p past 2^32 for the largest images)
+    for (uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x; p < npix; p += (uint64_t)gridDim.x * kBlock)
+        a.add_pixel(accum, accum_sq, cnt, p, floor3, stderr_rgb);
+    // (all 256 threads reach here: the loop above has no barrier)
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a.sum_rel = a.sum_rel + __shfl_down(a.sum_rel, off, 64);
-        a.sum_se2 = a.sum_se2 + __shfl_down(a.sum_se2, off, 64);
-        const double mx = __shfl_down(a.max_rel, off, 64);
-        if (mx > a.max_rel) a.max_rel = mx;
-        a.pixels += __shfl_down(a.pixels, off, 64);
-        a.nonfinite += __shfl_down(a.nonfinite, off, 64);
-    }
+    for (int off = 32; off > 0; off >>= 1)
+        a.merge(rtw_noise_acc{__shfl_down(a.sum_rel, off, 64), __shfl_down(a.max_rel, off, 64),
+                              __shfl_down(a.sum_se2, off, 64), __shfl_down(a.pixels, off, 64),
+                              __shfl_down(a.nonfinite, off, 64)});
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) {
-        noise_part t = s_part[0];
-        for (int w = 1; w < kWaves; ++w) {
-            t.sum_rel = t.sum_rel + s_part[w].sum_rel;
-            t.sum_se2 = t.sum_se2 + s_part[w].sum_se2;
-            if (s_part[w].max_rel > t.max_rel) t.max_rel = s_part[w].max_rel;
-            t.pixels += s_part[w].pixels;
-            t.nonfinite += s_part[w].nonfinite;
-        }
+        rtw_noise_acc t = s_part[0];
+        for (int w = 1; w < kWaves; ++w) t.merge(s_part[w]);
         parts[blockIdx.x] = t;
     }
-}
-
-__global__ __launch_bounds__(kBlock) void k_noise_pixels(const double* __restrict__ accum,
-                                                         const double* __restrict__ accum_sq, uint64_t npix,
-                                                         double dn, double dn1, double floor3,
-                                                         double* __restrict__ stderr_rgb,
-                                                         noise_part* __restrict__ parts) {
-    __shared__ noise_part s_part[kWaves];
-    noise_part a;
-    a.sum_rel = 0.0, a.max_rel = -__builtin_inf(), a.sum_se2 = 0.0, a.pixels = 0, a.nonfinite = 0;
-    // (64-bit p: the stride may carry p past 2^32 for the largest images)
-    for (uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x; p < npix; p += (uint64_t)gridDim.x * kBlock) {
-        double se[3], m[3];
-        bool finite = true;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double s1 = accum[3 * p + c], s2 = accum_sq[3 * p + c];
-            finite = finite && __builtin_isfinite(s1) && __builtin_isfinite(s2);
-            m[c] = s1 / dn;
-            double v = (s2 - s1 * m[c]) / dn1;
-            if (v < 0.0) v = 0.0;
-            se[c] = __builtin_sqrt(v / dn);
-        }
-        if (!finite) {
-            ++a.nonfinite;
-            if (stderr_rgb) {
-                const double nan = __builtin_nan("");
-                stderr_rgb[3 * p] = nan, stderr_rgb[3 * p + 1] = nan, stderr_rgb[3 * p + 2] = nan;
-            }
-            continue;
-        }
-        if (stderr_rgb) stderr_rgb[3 * p] = se[0], stderr_rgb[3 * p + 1] = se[1], stderr_rgb[3 * p + 2] = se[2];
-        const double rel = ((se[0] + se[1]) + se[2]) / (((m[0] + m[1]) + m[2]) + floor3);
-        ++a.pixels;
-        a.sum_rel = a.sum_rel + rel;
-        if (rel > a.max_rel) a.max_rel = rel;
-        a.sum_se2 = a.sum_se2 + ((se[0] * se[0] + se[1] * se[1]) + se[2] * se[2]);
-    }
-    // (all 256 threads reach here: the loop above has no barrier)
-    noise_fold(a, s_part, parts);
-}
-
-// ... with each pixel's own sample count n = counts[p] (rtw_adaptive.h
-// rtw_noise_estimate_counts: adaptive.h's rtw_pixel_rel, the host's
-// function): the same grid, the same per-thread pixel order and the same fold
-// as k_noise_pixels, so uniform counts give its bits.  A pixel with fewer than
-// two samples is left out as a non-finite one is.
-__global__ __launch_bounds__(kBlock) void k_noise_pixels_counts(const double* __restrict__ accum,
-                                                                const double* __restrict__ accum_sq,
-                                                                const uint32_t* __restrict__ counts, uint64_t npix,
-                                                                double floor3, double* __restrict__ stderr_rgb,
-                                                                noise_part* __restrict__ parts) {
-    __shared__ noise_part s_part[kWaves];
-    noise_part a;
-    a.sum_rel = 0.0, a.max_rel = -__builtin_inf(), a.sum_se2 = 0.0, a.pixels = 0, a.nonfinite = 0;
-    for (uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x; p < npix; p += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t n = counts[p];
-        double se[3], rel = 0.0;
-        bool finite = false;
-        if (n >= 2) {
-            const double s1[3] = {accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]};
-            const double s2[3] = {accum_sq[3 * p], accum_sq[3 * p + 1], accum_sq[3 * p + 2]};
-            rel = rtw_pixel_rel(s1, s2, (double)n, (double)(n - 1), floor3, se, &finite);
-        }
-        if (!finite) {
-            ++a.nonfinite;
-            if (stderr_rgb) {
-                const double nan = __builtin_nan("");
-                stderr_rgb[3 * p] = nan, stderr_rgb[3 * p + 1] = nan, stderr_rgb[3 * p + 2] = nan;
-            }
-            continue;
-        }
-        if (stderr_rgb) stderr_rgb[3 * p] = se[0], stderr_rgb[3 * p + 1] = se[1], stderr_rgb[3 * p + 2] = se[2];
-        ++a.pixels;
-        a.sum_rel = a.sum_rel + rel;
-        if (rel > a.max_rel) a.max_rel = rel;
-        a.sum_se2 = a.sum_se2 + ((se[0] * se[0] + se[1] * se[1]) + se[2] * se[2]);
-    }
-    noise_fold(a, s_part, parts);
 }
 
 // rtw_adaptive_select_device: the ascending list of the active pixels
@@ -1988,7 +1897,7 @@ uint64_t select_chunk(uint64_t npix) {
 }
 struct select_args {
     const double *accum, *accum_sq;
-    const uint32_t* counts;
+    rtw_count_src cnt;
     uint64_t npix, chunk;
     double floor3, target_rel;
     uint32_t max_count;
@@ -1997,7 +1906,7 @@ __device__ __forceinline__ bool select_flag(const select_args& A, uint64_t p) {
     if (p >= A.npix) return false;
     const double s1[3] = {A.accum[3 * p], A.accum[3 * p + 1], A.accum[3 * p + 2]};
     const double s2[3] = {A.accum_sq[3 * p], A.accum_sq[3 * p + 1], A.accum_sq[3 * p + 2]};
-    return rtw_pixel_active(s1, s2, A.counts[p], A.floor3, A.target_rel, A.max_count);
+    return rtw_pixel_active(s1, s2, A.cnt[p], A.floor3, A.target_rel, A.max_count);
 }
 __global__ __launch_bounds__(kBlock) void k_select_count(select_args A, uint32_t* __restrict__ block_counts) {
     __shared__ uint32_t s_wave[kWaves];
@@ -2054,7 +1963,7 @@ __global__ __launch_bounds__(kBlock) void k_select_scatter(select_args A, const 
 // the 3x3 variance blur is part of the pass (rtw_dn_pass).
 __global__ __launch_bounds__(kBlock) void k_denoise_prepare(const double* __restrict__ accum,
                                                             const double* __restrict__ accum_sq,
-                                                            const uint32_t* __restrict__ counts, uint32_t n,
+                                                            rtw_count_src cnt,
                                                             const double* __restrict__ features, double fs, double eps_a,
                                                             uint64_t npix, rtw_dn_state* __restrict__ st,
                                                             rtw_dn_geo* __restrict__ geo, rtw_dn_alb* __restrict__ alb) {
@@ -2068,7 +1977,7 @@ __global__ __launch_bounds__(kBlock) void k_denoise_prepare(const double* __rest
     rtw_dn_state s;
     rtw_dn_geo g;
     rtw_dn_alb a;
-    rtw_dn_prepare(s1, s2, counts ? counts[p] : n, f, fs, eps_a, s, g, a);
+    rtw_dn_prepare(s1, s2, cnt[p], f, fs, eps_a, s, g, a);
     st[p] = s, geo[p] = g, alb[p] = a;
 }
 
@@ -2160,27 +2069,18 @@ __global__ __launch_bounds__(kBlock) void k_denoise_finish(const rtw_dn_state* _
 // iterations == 0: the mean and the variance of the mean, no filter
 __global__ __launch_bounds__(kBlock) void k_denoise_mean(const double* __restrict__ accum,
                                                          const double* __restrict__ accum_sq,
-                                                         const uint32_t* __restrict__ counts, uint32_t n, uint64_t npix,
+                                                         rtw_count_src cnt, uint64_t npix,
                                                          double* __restrict__ out, double* __restrict__ out_var) {
     const uint64_t p = blockIdx.x * (uint64_t)kBlock + threadIdx.x;
     if (p >= npix) return;
     const double s1[3] = {accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]};
     const double s2[3] = {accum_sq[3 * p], accum_sq[3 * p + 1], accum_sq[3 * p + 2]};
     double m[3], v[3];
-    const bool ok = rtw_dn_moments(s1, s2, counts ? counts[p] : n, m, v);
+    const bool ok = rtw_pixel_moments(s1, s2, cnt[p], m, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         out[3 * p + c] = m[c];
         if (out_var) out_var[3 * p + c] = ok ? v[c] : __builtin_nan("");
-    }
-}
-
-// canvas = min(sqrt(mean), 1): k_finalize without the division
-__global__ __launch_bounds__(kBlock) void k_finalize_mean(const double* __restrict__ mean, size_t n,
-                                                          double* __restrict__ canvas) {
-    for (size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock) {
-        const double s = __builtin_sqrt(mean[k]);
-        canvas[k] = (1.0 < s) ? 1.0 : s;
     }
 }
 
@@ -2284,7 +2184,7 @@ struct handle_t {
     dev_buf accum;    // device accum when the caller passes a host pointer
     dev_buf run2;     // rtw_render_accumulate_moments: per-pixel running sums of squares
     dev_buf accum_sq; // ... device accum_sq when the caller passes a host pointer
-    dev_buf noise;    // rtw_noise_estimate_device: per-block partials (noise_part)
+    dev_buf noise;    // rtw_noise_estimate_device: per-block partials (rtw_noise_acc)
     // rtw_adaptive.h
     dev_buf alist;    // the device copy of a host pixel list; the adaptive loop's list
     dev_buf counts;   // the device copy of a host counts buffer; the adaptive loop's counts
@@ -2812,17 +2712,32 @@ extern "C" void rtw_scene_free(void* handle) {
     delete h;  // frees its buffers (dev_buf)
 }
 
+// The non-null ones of a call's device buffers belong to the handle's device.
+static int check_handle_ptrs(const handle_t* h, const char* what, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (p)
+            if (int rc = rtw_check_device_ptr(p, h->device, what)) return rc;
+    return RTW_OK;
+}
+
+// The canvas of an image's sums over a divisor source (k_finalize<D>);
+// returns when the kernel has ended.
+template <class D>
+static int launch_finalize(handle_t* h, const double* sums, int nx, int ny, D div, double* canvas) {
+    const size_t n = (size_t)nx * (size_t)ny * 3;
+    hipLaunchKernelGGL(k_finalize<D>, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, sums, n, div, canvas);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return RTW_OK;
+}
+
 extern "C" int rtw_finalize_canvas_device(void* handle, const double* accum, int nx, int ny, int spp,
                                           double* canvas) {
     handle_t* h = static_cast<handle_t*>(handle);
     if (!h || !accum || !canvas || nx <= 0 || ny <= 0 || spp <= 0)
         return rtw_fail(RTW_ERR_INVALID, "rtw_finalize_canvas_device: bad argument");
     HIPCHK(hipSetDevice(h->device));
-    const size_t n = (size_t)nx * (size_t)ny * 3;
-    hipLaunchKernelGGL(k_finalize, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, accum, n, (double)spp, canvas);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return RTW_OK;
+    return launch_finalize(h, accum, nx, ny, rtw_div_uniform{(double)spp}, canvas);
 }
 
 namespace {
@@ -3335,23 +3250,24 @@ extern "C" int rtw_render_accumulate_moments(void* handle, const rtw_camera_desc
     return render_accumulate(h, camera, prm, accum_rgb, accum_sq_rgb, out_stats);
 }
 
-// The summary of a launched k_noise_pixels[_counts]: the blocks' partials
-// copied out and added in block order (returns when the kernel has ended).
-static int noise_parts_summary(handle_t* h, unsigned grid, rtw_noise_summary* out) {
-    const noise_part* parts = static_cast<const noise_part*>(h->noise.p);
-    std::vector<noise_part> host(grid);
-    HIPCHK(hipMemcpyAsync(host.data(), parts, sizeof(noise_part) * grid, hipMemcpyDeviceToHost, h->stream));
+// k_noise_pixels over an image's moments, then the summary: the blocks'
+// partials copied out and merged in block order (returns when the kernel has
+// ended).
+static int estimate_device(handle_t* h, const double* accum, const double* accum_sq, rtw_count_src cnt, uint64_t npix,
+                           double floor, double* stderr_dev, rtw_noise_summary* out) {
+    const unsigned grid = noise_grid(npix);
+    if (int rc = h->noise.ensure(sizeof(rtw_noise_acc) * kNoiseMaxGrid)) return rc;
+    rtw_noise_acc* parts = static_cast<rtw_noise_acc*>(h->noise.p);
+    hipLaunchKernelGGL(k_noise_pixels, dim3(grid), dim3(kBlock), 0, h->stream, accum, accum_sq, cnt, npix, 3.0 * floor,
+                       stderr_dev, parts);
+    HIPCHK(hipGetLastError());
+    std::vector<rtw_noise_acc> host(grid);
+    HIPCHK(hipMemcpyAsync(host.data(), parts, sizeof(rtw_noise_acc) * grid, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (out) {
-        noise_part t = host[0];  // the blocks' partials, in block order
-        for (unsigned b = 1; b < grid; ++b) {
-            t.sum_rel = t.sum_rel + host[b].sum_rel;
-            t.sum_se2 = t.sum_se2 + host[b].sum_se2;
-            if (host[b].max_rel > t.max_rel) t.max_rel = host[b].max_rel;
-            t.pixels += host[b].pixels;
-            t.nonfinite += host[b].nonfinite;
-        }
-        rtw_noise_finish(t.pixels, t.nonfinite, t.sum_rel, t.max_rel, t.sum_se2, out);
+        rtw_noise_acc t = host[0];
+        for (unsigned b = 1; b < grid; ++b) t.merge(host[b]);
+        rtw_noise_finish(t, out);
     }
     return RTW_OK;
 }
@@ -3359,22 +3275,13 @@ static int noise_parts_summary(handle_t* h, unsigned grid, rtw_noise_summary* ou
 extern "C" int rtw_noise_estimate_device(void* handle, const double* accum, const double* accum_sq, int nx, int ny,
                                          int n, double floor, double* stderr_dev, rtw_noise_summary* out) {
     handle_t* h = static_cast<handle_t*>(handle);
-    if (!h) return rtw_fail(RTW_ERR_INVALID, "rtw_noise_estimate_device: null scene handle");
-    if (int rc = rtw_noise_check_args("rtw_noise_estimate_device", accum, accum_sq, nx, ny, n, floor, stderr_dev))
-        return rc;
+    const char* const what = "rtw_noise_estimate_device";
+    if (!h) return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": null scene handle");
+    if (int rc = rtw_noise_check_args(what, accum, accum_sq, nx, ny, n, floor, stderr_dev)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    if (int rc = rtw_check_device_ptr(accum, h->device, "rtw_noise_estimate_device")) return rc;
-    if (int rc = rtw_check_device_ptr(accum_sq, h->device, "rtw_noise_estimate_device")) return rc;
-    if (stderr_dev)
-        if (int rc = rtw_check_device_ptr(stderr_dev, h->device, "rtw_noise_estimate_device")) return rc;
-    const uint64_t npix = (uint64_t)nx * (uint64_t)ny;
-    const unsigned grid = noise_grid(npix);
-    if (int rc = h->noise.ensure(sizeof(noise_part) * kNoiseMaxGrid)) return rc;
-    noise_part* parts = static_cast<noise_part*>(h->noise.p);
-    hipLaunchKernelGGL(k_noise_pixels, dim3(grid), dim3(kBlock), 0, h->stream, accum, accum_sq, npix, (double)n,
-                       (double)(n - 1), 3.0 * floor, stderr_dev, parts);
-    HIPCHK(hipGetLastError());
-    return noise_parts_summary(h, grid, out);
+    if (int rc = check_handle_ptrs(h, what, {accum, accum_sq, stderr_dev})) return rc;
+    return estimate_device(h, accum, accum_sq, rtw_count_src{nullptr, (uint32_t)n}, (uint64_t)nx * (uint64_t)ny, floor,
+                           stderr_dev, out);
 }
 
 // ======================================================================
@@ -3408,15 +3315,6 @@ extern "C" int rtw_scene_query_active(void* handle, int precision, char name[128
     return RTW_OK;
 }
 
-// The device buffers of a select / estimate / finalize call belong to the
-// handle's device.
-static int check_adaptive_ptrs(const handle_t* h, const char* what, std::initializer_list<const void*> ptrs) {
-    for (const void* p : ptrs)
-        if (p)
-            if (int rc = rtw_check_device_ptr(p, h->device, what)) return rc;
-    return RTW_OK;
-}
-
 // The select's three launches into active_dev; the length lands in *n_out
 // when the stream has run them (the caller synchronises).
 static int launch_select(handle_t* h, const double* accum, const double* accum_sq, const uint32_t* counts, uint64_t npix,
@@ -3425,7 +3323,8 @@ static int launch_select(handle_t* h, const double* accum, const double* accum_s
     uint32_t* block_counts = static_cast<uint32_t*>(h->sel.p) + 1;  // ([0]: the list check's flag)
     uint32_t* offsets = block_counts + kSelectMaxGrid;
     const unsigned grid = select_grid(npix);
-    const select_args A{accum, accum_sq, counts, npix, select_chunk(npix), 3.0 * floor, target_rel, max_count};
+    const select_args A{accum, accum_sq, rtw_count_src{counts, 0}, npix, select_chunk(npix), 3.0 * floor, target_rel,
+                        max_count};
     hipStream_t st = h->stream;
     hipLaunchKernelGGL(k_select_count, dim3(grid), dim3(kBlock), 0, st, A, block_counts);
     hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(kBlock), 0, st, block_counts, (uint32_t)grid, offsets);
@@ -3445,7 +3344,7 @@ extern "C" int rtw_adaptive_select_device(void* handle, const double* accum, con
                                            n_active_host))
         return rc;
     HIPCHK(hipSetDevice(h->device));
-    if (int rc = check_adaptive_ptrs(h, what, {accum, accum_sq, counts, active_dev})) return rc;
+    if (int rc = check_handle_ptrs(h, what, {accum, accum_sq, counts, active_dev})) return rc;
     uint32_t n = 0;
     if (int rc = launch_select(h, accum, accum_sq, counts, (uint64_t)nx * (uint64_t)ny, floor, target_rel, max_count,
                                active_dev, &n))
@@ -3453,16 +3352,6 @@ extern "C" int rtw_adaptive_select_device(void* handle, const double* accum, con
     HIPCHK(hipStreamSynchronize(h->stream));
     *n_active_host = n;
     return RTW_OK;
-}
-
-static int estimate_counts_device(handle_t* h, const double* accum, const double* accum_sq, const uint32_t* counts,
-                                  uint64_t npix, double floor, double* stderr_dev, rtw_noise_summary* out) {
-    const unsigned grid = noise_grid(npix);
-    if (int rc = h->noise.ensure(sizeof(noise_part) * kNoiseMaxGrid)) return rc;
-    hipLaunchKernelGGL(k_noise_pixels_counts, dim3(grid), dim3(kBlock), 0, h->stream, accum, accum_sq, counts, npix,
-                       3.0 * floor, stderr_dev, static_cast<noise_part*>(h->noise.p));
-    HIPCHK(hipGetLastError());
-    return noise_parts_summary(h, grid, out);
 }
 
 extern "C" int rtw_noise_estimate_counts_device(void* handle, const double* accum, const double* accum_sq,
@@ -3473,8 +3362,9 @@ extern "C" int rtw_noise_estimate_counts_device(void* handle, const double* accu
     if (!h) return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": null scene handle");
     if (int rc = rtw_adaptive_check_estimate(what, accum, accum_sq, counts, nx, ny, floor, stderr_dev)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    if (int rc = check_adaptive_ptrs(h, what, {accum, accum_sq, counts, stderr_dev})) return rc;
-    return estimate_counts_device(h, accum, accum_sq, counts, (uint64_t)nx * (uint64_t)ny, floor, stderr_dev, out);
+    if (int rc = check_handle_ptrs(h, what, {accum, accum_sq, counts, stderr_dev})) return rc;
+    return estimate_device(h, accum, accum_sq, rtw_count_src{counts, 0}, (uint64_t)nx * (uint64_t)ny, floor, stderr_dev,
+                           out);
 }
 
 extern "C" int rtw_finalize_canvas_counts_device(void* handle, const double* accum, const uint32_t* counts, int nx,
@@ -3484,12 +3374,8 @@ extern "C" int rtw_finalize_canvas_counts_device(void* handle, const double* acc
     if (!h || !accum || !counts || !canvas || nx <= 0 || ny <= 0)
         return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": bad argument");
     HIPCHK(hipSetDevice(h->device));
-    if (int rc = check_adaptive_ptrs(h, what, {accum, counts, canvas})) return rc;
-    const size_t n = (size_t)nx * (size_t)ny * 3;
-    hipLaunchKernelGGL(k_finalize_counts, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, accum, counts, n, canvas);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return RTW_OK;
+    if (int rc = check_handle_ptrs(h, what, {accum, counts, canvas})) return rc;
+    return launch_finalize(h, accum, nx, ny, rtw_div_counts{counts}, canvas);
 }
 
 static void add_stats(rtw_stats& t, const rtw_stats& s) {
@@ -3525,7 +3411,7 @@ extern "C" int rtw_render_adaptive(void* handle, const rtw_camera_desc* camera, 
     double *a_dev = accum_rgb, *q_dev = accum_sq_rgb;
     uint32_t* c_dev = counts;
     if (on_device) {
-        if (int rc = check_adaptive_ptrs(h, what, {accum_rgb, accum_sq_rgb, counts})) return rc;
+        if (int rc = check_handle_ptrs(h, what, {accum_rgb, accum_sq_rgb, counts})) return rc;
     } else {
         if (int rc = h->accum.ensure(img)) return rc;
         if (int rc = h->accum_sq.ensure(img)) return rc;
@@ -3574,7 +3460,8 @@ extern "C" int rtw_render_adaptive(void* handle, const rtw_camera_desc* camera, 
     // the summary is the estimate of the buffers the caller gets back: the
     // device estimator's for device buffers, the host's for host buffers
     if (on_device)
-        if (int rc = estimate_counts_device(h, a_dev, q_dev, c_dev, npix, ap->floor, nullptr, &res.final)) return rc;
+        if (int rc = estimate_device(h, a_dev, q_dev, rtw_count_src{c_dev, 0}, npix, ap->floor, nullptr, &res.final))
+            return rc;
     std::vector<uint32_t> c_host;
     uint32_t* c_read = counts;
     if (on_device) {
@@ -3704,12 +3591,13 @@ extern "C" int rtw_denoise_device(void* handle, const double* accum, const doubl
     if (int rc = rtw_denoise_check_args(what, accum, accum_sq, counts, n, features, feature_spp, nx, ny, prm, out, out_var))
         return rc;
     HIPCHK(hipSetDevice(h->device));
-    if (int rc = check_adaptive_ptrs(h, what, {accum, accum_sq, counts, features, out, out_var})) return rc;
+    if (int rc = check_handle_ptrs(h, what, {accum, accum_sq, counts, features, out, out_var})) return rc;
     const uint64_t npix = (uint64_t)nx * (uint64_t)ny;
+    const rtw_count_src cnt{counts, (uint32_t)n};
     const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock)), block(kBlock);
     hipStream_t st = h->stream;
     if (prm->iterations == 0) {
-        hipLaunchKernelGGL(k_denoise_mean, grid, block, 0, st, accum, accum_sq, counts, (uint32_t)n, npix, out, out_var);
+        hipLaunchKernelGGL(k_denoise_mean, grid, block, 0, st, accum, accum_sq, cnt, npix, out, out_var);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
         return RTW_OK;
@@ -3737,8 +3625,8 @@ extern "C" int rtw_denoise_device(void* handle, const double* accum, const doubl
         return RTW_OK;
     };
     if (int rc = mark()) return rc;
-    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, st, accum, accum_sq, counts, (uint32_t)n, features,
-                       (double)feature_spp, prm->eps_a, npix, a, geo, alb);
+    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, st, accum, accum_sq, cnt, features, (double)feature_spp,
+                       prm->eps_a, npix, a, geo, alb);
     if (int rc = mark()) return rc;
     const dim3 tgrid((unsigned)((nx + kTileX - 1) / kTileX), (unsigned)((ny + kTileY - 1) / kTileY));
     for (int k = 0; k < prm->iterations; ++k) {
@@ -3779,10 +3667,6 @@ extern "C" int rtw_finalize_canvas_mean_device(void* handle, const double* mean,
     const char* const what = "rtw_finalize_canvas_mean_device";
     if (!h || !mean || !canvas || nx <= 0 || ny <= 0) return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": bad argument");
     HIPCHK(hipSetDevice(h->device));
-    if (int rc = check_adaptive_ptrs(h, what, {mean, canvas})) return rc;
-    const size_t n = (size_t)nx * (size_t)ny * 3;
-    hipLaunchKernelGGL(k_finalize_mean, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, mean, n, canvas);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return RTW_OK;
+    if (int rc = check_handle_ptrs(h, what, {mean, canvas})) return rc;
+    return launch_finalize(h, mean, nx, ny, rtw_div_none{}, canvas);
 }

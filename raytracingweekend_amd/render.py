@@ -152,15 +152,25 @@ class DeviceScene:
         estimator (rtw_noise_estimate_device; the map is a tensor); numpy
         arrays fall through to the host function, render.noise_estimate.
         Returns (stderr or None, summary dict)."""
+        return self._noise_estimate(accum, accum_sq, nx, ny, floor, want_stderr, n=n)
+
+    def _noise_estimate(self, accum, accum_sq, nx: int, ny: int, floor: float, want_stderr: bool, n=None, counts=None):
+        """noise_estimate (n) and noise_estimate_counts (counts): numpy arrays
+        go to the host functions, tensors to the device entry points."""
         if isinstance(accum, np.ndarray) and isinstance(accum_sq, np.ndarray):
-            return noise_estimate(accum, accum_sq, nx, ny, n, floor, want_stderr)
+            return _noise_estimate(accum, accum_sq, nx, ny, floor, want_stderr, n, counts)
         ptr, ptr_sq, _ = self._moment_buffers(accum, accum_sq, nx, ny)
         import torch
         se = torch.empty_like(accum) if want_stderr else None
         out = _abi.rtw_noise_summary()
-        check(lib().rtw_noise_estimate_device(self.handle, ptr, ptr_sq, nx, ny, n, floor,
-                                              C.c_void_p(se.data_ptr()) if want_stderr else None, C.byref(out)),
-              "rtw_noise_estimate_device")
+        tail = (floor, C.c_void_p(se.data_ptr()) if want_stderr else None, C.byref(out))
+        if counts is None:
+            check(lib().rtw_noise_estimate_device(self.handle, ptr, ptr_sq, nx, ny, n, *tail),
+                  "rtw_noise_estimate_device")
+        else:
+            check(lib().rtw_noise_estimate_counts_device(self.handle, ptr, ptr_sq,
+                                                         self._u32_ptr(counts, nx * ny, "counts", True), nx, ny, *tail),
+                  "rtw_noise_estimate_counts_device")
         return se, out.as_dict()
 
     # ---- adaptive sampling (include/rtw_adaptive.h) ---------------------------
@@ -237,31 +247,34 @@ class DeviceScene:
                               want_stderr: bool = True):
         """noise_estimate with a per-pixel sample count (rtw_noise_estimate_counts
         [_device]).  Returns (stderr or None, summary dict)."""
-        if isinstance(accum, np.ndarray):
-            return noise_estimate_counts(accum, accum_sq, counts, nx, ny, floor, want_stderr)
-        import torch
-        ptr, ptr_sq, _ = self._moment_buffers(accum, accum_sq, nx, ny)
-        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", True)
-        se = torch.empty_like(accum) if want_stderr else None
-        out = _abi.rtw_noise_summary()
-        check(lib().rtw_noise_estimate_counts_device(self.handle, ptr, ptr_sq, ptr_counts, nx, ny, floor,
-                                                     C.c_void_p(se.data_ptr()) if want_stderr else None,
-                                                     C.byref(out)), "rtw_noise_estimate_counts_device")
-        return se, out.as_dict()
+        return self._noise_estimate(accum, accum_sq, nx, ny, floor, want_stderr, counts=counts)
 
     def finalize_counts(self, accum, counts, nx: int, ny: int):
         """canvas = min(sqrt(accum / counts[p]), 1) (rtw_finalize_canvas_counts
         [_device]): a tensor for tensors, an array for arrays."""
-        if isinstance(accum, np.ndarray):
-            return finalize_counts(accum, counts, nx, ny)
+        return self._finalize(accum, nx, ny, "accum", counts=counts)
+
+    def _finalize(self, sums, nx: int, ny: int, name: str, n=None, counts=None, canvas=None):
+        """The canvas of channel sums over `n` samples, over counts[p], or of
+        a mean (neither): numpy arrays go to the host functions, tensors to
+        the device entry points (into `canvas`, if given)."""
+        if isinstance(sums, np.ndarray):
+            return _finalize(sums, nx, ny, n, counts)
         import torch
-        ptr, _ = self._accum_ptr(accum, nx, ny, "accum")
-        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", True)
-        canvas = torch.empty_like(accum)
-        torch.cuda.synchronize(accum.device)
-        check(lib().rtw_finalize_canvas_counts_device(self.handle, ptr, ptr_counts, nx, ny,
-                                                      C.c_void_p(canvas.data_ptr())),
-              "rtw_finalize_canvas_counts_device")
+        ptr, _ = self._accum_ptr(sums, nx, ny, name)
+        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", True) if counts is not None else None
+        if canvas is None:
+            canvas = torch.empty_like(sums)
+        torch.cuda.synchronize(sums.device)
+        out = C.c_void_p(canvas.data_ptr())
+        if counts is not None:
+            check(lib().rtw_finalize_canvas_counts_device(self.handle, ptr, ptr_counts, nx, ny, out),
+                  "rtw_finalize_canvas_counts_device")
+        elif n is not None:
+            check(lib().rtw_finalize_canvas_device(self.handle, ptr, nx, ny, n, out), "rtw_finalize_canvas_device")
+        else:
+            check(lib().rtw_finalize_canvas_mean_device(self.handle, ptr, nx, ny, out),
+                  "rtw_finalize_canvas_mean_device")
         return canvas
 
     def query_active(self, precision: str = "fp64") -> str:
@@ -342,29 +355,14 @@ class DeviceScene:
     def finalize_mean(self, mean, nx: int, ny: int):
         """canvas = min(sqrt(mean), 1) of a denoised mean
         (rtw_finalize_canvas_mean[_device])."""
-        if isinstance(mean, np.ndarray):
-            return finalize_mean(mean, nx, ny)
-        import torch
-        ptr, _ = self._accum_ptr(mean, nx, ny, "mean")
-        canvas = torch.empty_like(mean)
-        torch.cuda.synchronize(mean.device)
-        check(lib().rtw_finalize_canvas_mean_device(self.handle, ptr, nx, ny, C.c_void_p(canvas.data_ptr())),
-              "rtw_finalize_canvas_mean_device")
-        return canvas
+        return self._finalize(mean, nx, ny, "mean")
 
     def finalize_device(self, accum, nx: int, ny: int, spp: int, canvas=None):
         """canvas = min(sqrt(accum / spp), 1) on the GPU (torch float64 CUDA
         tensors of nx*ny*3 on this device).  Returns the canvas tensor."""
-        import torch
-        if not (accum.is_cuda and accum.dtype == torch.float64 and accum.numel() == nx * ny * 3
-                and accum.is_contiguous()):
+        if isinstance(accum, np.ndarray) or not accum.is_cuda:
             raise ValueError("accum must be a contiguous float64 CUDA tensor of nx*ny*3")
-        if canvas is None:
-            canvas = torch.empty_like(accum)
-        torch.cuda.synchronize(accum.device)
-        check(lib().rtw_finalize_canvas_device(self.handle, C.c_void_p(accum.data_ptr()), nx, ny, spp,
-                                               C.c_void_p(canvas.data_ptr())), "rtw_finalize_canvas_device")
-        return canvas
+        return self._finalize(accum, nx, ny, "accum", n=spp, canvas=canvas)
 
     def query(self) -> dict:
         """rtw_scene_query: run layout, feature bits, the traversal kernel a
@@ -458,9 +456,25 @@ def device_count() -> int:
 def finalize(accum: np.ndarray, nx: int, ny: int, spp: int) -> np.ndarray:
     """canvas = min(sqrt(sum / spp), 1) (RayTracingWeekend.cpp:241-244), via the
     library's rtw_finalize_canvas."""
-    a = np.ascontiguousarray(accum, dtype=np.float64)
+    return _finalize(accum, nx, ny, n=spp)
+
+
+def _finalize(sums, nx: int, ny: int, n=None, counts=None) -> np.ndarray:
+    """The host canvas of channel sums over `n` samples (unchecked, as the
+    reference's), over counts[p], or of a mean (neither)."""
+    a = np.ascontiguousarray(sums, dtype=np.float64)
+    c = np.ascontiguousarray(counts, dtype=np.uint32) if counts is not None else None
+    if n is None and (a.size != nx * ny * 3 or (c is not None and c.size != nx * ny)):
+        raise ValueError("the sums (or the mean) must hold nx*ny*3 values and counts nx*ny")
     out = np.empty(nx * ny * 3, dtype=np.float64)
-    lib().rtw_finalize_canvas(a.ctypes.data_as(C.c_void_p), nx, ny, spp, out.ctypes.data_as(C.c_void_p))
+    pa, po = a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+    if c is not None:
+        check(lib().rtw_finalize_canvas_counts(pa, c.ctypes.data_as(C.c_void_p), nx, ny, po),
+              "rtw_finalize_canvas_counts")
+    elif n is not None:
+        lib().rtw_finalize_canvas(pa, nx, ny, n, po)
+    else:
+        check(lib().rtw_finalize_canvas_mean(pa, nx, ny, po), "rtw_finalize_canvas_mean")
     return out
 
 
@@ -478,15 +492,25 @@ def noise_estimate(accum: np.ndarray, accum_sq: np.ndarray, nx: int, ny: int, n:
     mean and the image-wide summary {pixels, nonfinite, mean_rel, max_rel,
     rms_stderr} (include/rtw_noise.h).  Returns (stderr array or None,
     summary dict)."""
+    return _noise_estimate(accum, accum_sq, nx, ny, floor, want_stderr, n=n)
+
+
+def _noise_estimate(accum, accum_sq, nx: int, ny: int, floor: float, want_stderr: bool, n=None, counts=None):
+    """The host estimate with `n` samples in every pixel, or counts[p]."""
     a = np.ascontiguousarray(accum, dtype=np.float64)
     q = np.ascontiguousarray(accum_sq, dtype=np.float64)
     if a.size != nx * ny * 3 or q.size != nx * ny * 3:
         raise ValueError("accum and accum_sq must hold nx*ny*3 values")
     se = np.empty(nx * ny * 3, dtype=np.float64) if want_stderr else None
     out = _abi.rtw_noise_summary()
-    check(lib().rtw_noise_estimate(a.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), nx, ny, n, floor,
-                                   se.ctypes.data_as(C.c_void_p) if want_stderr else None, C.byref(out)),
-          "rtw_noise_estimate")
+    pa, pq = a.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p)
+    tail = (floor, se.ctypes.data_as(C.c_void_p) if want_stderr else None, C.byref(out))
+    if counts is None:
+        check(lib().rtw_noise_estimate(pa, pq, nx, ny, n, *tail), "rtw_noise_estimate")
+    else:
+        _, _, c = _moments_counts(a, q, counts, nx, ny)
+        check(lib().rtw_noise_estimate_counts(pa, pq, c.ctypes.data_as(C.c_void_p), nx, ny, *tail),
+              "rtw_noise_estimate_counts")
     return se, out.as_dict()
 
 
@@ -562,23 +586,12 @@ def noise_estimate_counts(accum, accum_sq, counts, nx: int, ny: int, floor: floa
     """rtw_noise_estimate_counts on the host: noise_estimate with each pixel's
     own sample count; pixels with fewer than two samples are left out (counted
     in `nonfinite`).  Returns (stderr array or None, summary dict)."""
-    a, q, c = _moments_counts(accum, accum_sq, counts, nx, ny)
-    se = np.empty(nx * ny * 3, dtype=np.float64) if want_stderr else None
-    out = _abi.rtw_noise_summary()
-    check(lib().rtw_noise_estimate_counts(a.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p),
-                                          c.ctypes.data_as(C.c_void_p), nx, ny, floor,
-                                          se.ctypes.data_as(C.c_void_p) if want_stderr else None, C.byref(out)),
-          "rtw_noise_estimate_counts")
-    return se, out.as_dict()
+    return _noise_estimate(accum, accum_sq, nx, ny, floor, want_stderr, counts=counts)
 
 
 def finalize_counts(accum, counts, nx: int, ny: int) -> np.ndarray:
     """canvas = min(sqrt(sum / counts[p]), 1) via rtw_finalize_canvas_counts."""
-    a, _, c = _moments_counts(accum, None, counts, nx, ny)
-    out = np.empty(nx * ny * 3, dtype=np.float64)
-    check(lib().rtw_finalize_canvas_counts(a.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), nx, ny,
-                                           out.ctypes.data_as(C.c_void_p)), "rtw_finalize_canvas_counts")
-    return out
+    return _finalize(accum, nx, ny, counts=counts)
 
 
 def _adaptive_params(target_rel: float, floor: float, min_spp: int, max_spp: int, batch: int):
@@ -712,13 +725,7 @@ def denoise(accum, accum_sq, features, nx: int, ny: int, *, n: int = 0, counts=N
 
 def finalize_mean(mean, nx: int, ny: int) -> np.ndarray:
     """canvas = min(sqrt(mean), 1) via rtw_finalize_canvas_mean."""
-    m = np.ascontiguousarray(mean, dtype=np.float64)
-    if m.size != nx * ny * 3:
-        raise ValueError("mean must hold nx*ny*3 values")
-    out = np.empty(nx * ny * 3, dtype=np.float64)
-    check(lib().rtw_finalize_canvas_mean(m.ctypes.data_as(C.c_void_p), nx, ny, out.ctypes.data_as(C.c_void_p)),
-          "rtw_finalize_canvas_mean")
-    return out
+    return _finalize(mean, nx, ny)
 
 
 def render_denoised(ds, nx: int, ny: int, spp: int, max_depth: int, seed: int = 0, *, precision: str = "fp64",
