@@ -98,7 +98,12 @@ typedef enum rtw_entry_kind {
  * rects; translate(rotate_y(box)) is a group of six with two ops. */
 typedef struct rtw_entry {
     int32_t kind;           /* rtw_entry_kind                                  */
-    int32_t first_prim;
+    int32_t first_prim;     /* ranges are disjoint and ascend with the entry
+                               index: entries[e].first_prim >= entries[e - 1]
+                               .first_prim + entries[e - 1].n_prims, so that
+                               prim index order is list order (hits at equal
+                               distance are decided by it); rtw_scene_upload
+                               refuses another order, RTW_ERR_UNSUPPORTED     */
     int32_t n_prims;
     int32_t n_ops;
     int32_t op[RTW_MAX_OPS];
@@ -419,7 +424,10 @@ uint32_t rtw_path_seed(uint64_t seed, uint32_t pixel, uint32_t s);
 /* Build one of the reference scenes with the host C++ hittable API and
  * flatten it.  names: "cornell_box", "random_balls", "dielectric",
  * "light_sample", "book2_final", "textured" (a test scene of image textures
- * on every primitive kind).  `aspect` = nx/ny (Scene/scene.h ctor arg).
+ * on every primitive kind), and the other test scenes "nested",
+ * "nested_plain", "grouped", "grouped_world", "ties", "ties_axis" (coincident
+ * and touching primitives: hits at equal distance) and "probe_<kind>"
+ * (csrc/host/rtw/scene.h).  `aspect` = nx/ny (Scene/scene.h ctor arg).
  * `use_bvh` builds BVHs over the world / large groups.  The returned desc is
  * owned by the library; free it with rtw_scene_desc_free. */
 int rtw_scene_builtin(const char* name, double aspect, int use_bvh, rtw_scene_desc** out_desc);

@@ -32,7 +32,7 @@ REF = ROOT / "oracle" / "_ref" / "rtw_ref"
 OUT = ROOT / "tests" / "golden"
 
 SCENES = [("cornell_box", 1.0), ("random_balls", 1.5), ("dielectric", 2.0), ("light_sample", 2.0),
-          ("book2_final", 1.0), ("nested", 1.0), ("nested_plain", 1.0)]
+          ("book2_final", 1.0), ("nested", 1.0), ("nested_plain", 1.0), ("ties", 48 / 32)]
 
 PROBE_KINDS = ["rect_light", "sphere_light", "far_sphere_light", "default_light", "glass", "metal", "medium",
                "motion", "textures"]
@@ -56,6 +56,9 @@ RENDERS = [
     # the group-BVH test scenes (ours, composed in ref_harness.cpp)
     ("grouped_32x24x4_d50", "grouped", 32, 24, 4, 50, 0),
     ("grouped_world_32x24x4_d50", "grouped_world", 32, 24, 4, 50, 2),
+    # coincident primitives (ours, composed in ref_harness.cpp): hits at equal distance
+    ("ties_48x32x4_d50", "ties", 48, 32, 4, 50, 41),
+    ("ties_normal_48x32x4", "ties", 48, 32, 4, 50, 42, "normal"),
     # RenderType::Normal: 0.5 (n + 1) at the first hit
     ("cornell_normal_32x32x4", "cornell_box", 32, 32, 4, 50, 0, "normal"),
     ("random_balls_normal_48x32x4", "random_balls", 48, 32, 4, 50, 1, "normal"),

@@ -32,6 +32,7 @@
 // A scene name "normal:<name>" is <name> with RenderType::Normal.
 // "probe_<kind>" are the probe scenes (probe_ref_scene below), and
 // "probe_motion_narrow" is probe_motion with the camera's shutter [0.25, 0.5].
+// "ties" is the scene of coincident primitives (ties_ref_scene below).
 #include "rng_inject.h"
 
 #include <cfloat>
@@ -285,6 +286,98 @@ public:
 };
 
 // ---------------------------------------------------------------------------
+// "ties" (ours; scenes.cpp ties_scene builds the same with the library's host
+// API, and says what each category is for): twins, primitives of identical
+// geometry that differ in material and normal, in every class and walk.  The
+// same literals and the same order of Add calls as there.
+// ---------------------------------------------------------------------------
+class ties_ref_scene : public scene {
+    typedef std::shared_ptr<material> mat_ptr;
+    static mat_ptr diffuse(double r, double g, double b) {
+        return std::make_shared<lambertian>(std::make_shared<constant_texture>(vec3(r, g, b)));
+    }
+    static mat_ptr mirror() { return std::make_shared<metal>(vec3(0.9, 0.9, 0.9), 0.0); }
+    static std::shared_ptr<hittable> twin_mover(const vec3& c0, const vec3& c1, double r, mat_ptr m) {
+        auto ms = std::make_shared<moving_sphere>(c0, r, m);
+        movement_linear mv;
+        mv.center1 = c1;
+        mv.time0 = 0.0;
+        mv.time1 = 1.0;
+        ms->set_movement(mv);
+        return ms;
+    }
+
+public:
+    ties_ref_scene(double aspect) : scene() {
+        typedef std::vector<std::shared_ptr<hittable>> list;
+        const vec3 zero(0.0, 0.0, 0.0);
+        Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+        // a
+        Add(std::make_shared<sphere>(vec3(-4.0, 0.6, 0.0), 0.6, diffuse(0.8, 0.2, 0.2)));
+        Add(std::make_shared<sphere>(vec3(-4.0, 0.6, 0.0), -0.6, mirror()));
+        // c
+        Add(twin_mover(vec3(-2.5, 0.5, 0.25), vec3(-2.5, 0.9, 0.25), 0.5, diffuse(0.2, 0.7, 0.3)));
+        Add(twin_mover(vec3(-2.5, 0.5, 0.25), vec3(-2.5, 0.9, 0.25), -0.5, mirror()));
+        // d
+        Add(std::make_shared<sphere>(vec3(-1.0, 0.6, 0.0), 0.6, diffuse(0.2, 0.3, 0.8)));
+        Add(std::make_shared<translate>(std::make_shared<sphere>(vec3(-1.0, 0.6, 0.0), -0.6, mirror()), zero));
+        Add(std::make_shared<translate>(std::make_shared<sphere>(vec3(0.5, 0.6, 0.0), 0.6, diffuse(0.8, 0.7, 0.2)),
+                                        zero));
+        Add(std::make_shared<sphere>(vec3(0.5, 0.6, 0.0), -0.6, mirror()));
+        // b
+        Add(std::make_shared<sphere>(vec3(2.5, 0.0, 2.5), 0.7, diffuse(0.7, 0.3, 0.7)));
+        Add(std::make_shared<sphere>(vec3(2.5, 0.0, 2.5), -0.7, mirror()));
+        // c'
+        Add(twin_mover(vec3(-3.6, 0.4, 2.5), vec3(-3.3, 0.4, 2.5), 0.4, diffuse(0.3, 0.7, 0.7)));
+        Add(twin_mover(vec3(-3.6, 0.4, 2.5), vec3(-3.3, 0.4, 2.5), -0.4, mirror()));
+        // e
+        Add(std::make_shared<xy_rect>(1.5, 3.0, 0.0, 1.5, -0.5, diffuse(0.8, 0.5, 0.2)));
+        Add(std::make_shared<flip_normals>(std::make_shared<xy_rect>(1.5, 3.0, 0.0, 1.5, -0.5, mirror())));
+        Add(std::make_shared<xy_rect>(2.25, 3.5, 0.5, 2.0, -0.5, diffuse(0.2, 0.8, 0.5)));
+        // f
+        Add(std::make_shared<yz_rect>(0.0, 2.0, -1.0, 1.5, 4.0, diffuse(0.5, 0.2, 0.8)));
+        Add(std::make_shared<rotate_y>(
+            std::make_shared<flip_normals>(std::make_shared<yz_rect>(0.0, 2.0, -1.0, 1.5, 4.0, mirror())), 0.0));
+        Add(std::make_shared<rotate_y>(std::make_shared<xz_rect>(-1.0, 1.0, 4.5, 6.5, 0.2, diffuse(0.8, 0.8, 0.3)),
+                                       0.0));
+        Add(std::make_shared<flip_normals>(std::make_shared<xz_rect>(-1.0, 1.0, 4.5, 6.5, 0.2, mirror())));
+        // g
+        list balls;
+        for (int k = 0; k < 5; ++k) {
+            const vec3 c(-2.0 + k, 0.3, 0.0);
+            std::shared_ptr<hittable> plain =
+                std::make_shared<sphere>(c, 0.3, diffuse(0.3 + 0.1 * k, 0.6, 0.9 - 0.15 * k));
+            std::shared_ptr<hittable> twin = std::make_shared<sphere>(c, -0.3, mirror());
+            if (k & 1)
+                balls.push_back(twin), balls.push_back(plain);
+            else
+                balls.push_back(plain), balls.push_back(twin);
+            // a third coincident sphere: three items of one centre part 1 + 2 into leaves of two
+            if (k == 2) balls.push_back(std::make_shared<sphere>(c, 0.3, std::make_shared<dielectric>(1.5)));
+        }
+        Add(std::make_shared<translate>(std::make_shared<hittable_list>(balls), vec3(0.0, 0.0, 2.0)));
+        // h
+        list crates;
+        for (int k = 0; k < 5; ++k) {
+            const vec3 p0(k, 0.0, 0.0), p1(k + 1.0, 0.3 + 0.05 * k, 0.6);
+            std::shared_ptr<hittable> plain =
+                std::make_shared<box>(p0, p1, diffuse(0.9 - 0.15 * k, 0.4, 0.2 + 0.15 * k));
+            std::shared_ptr<hittable> twin = std::make_shared<flip_normals>(std::make_shared<box>(p0, p1, mirror()));
+            // a third coincident box, first in the list (the last one wins)
+            if (k == 2) crates.push_back(std::make_shared<box>(p0, p1, std::make_shared<dielectric>(1.5)));
+            if (k & 1)
+                crates.push_back(twin), crates.push_back(plain);
+            else
+                crates.push_back(plain), crates.push_back(twin);
+        }
+        Add(std::make_shared<translate>(std::make_shared<hittable_list>(crates), vec3(-2.5, 0.0, 3.2)));
+
+        this->cam = camera(vec3(0.0, 2.5, 10.0), vec3(0.0, 0.6, 0.0), vec3(0.0, 1.0, 0.0), 38.0, aspect, 0.0, 10.0,
+                           0.0, 1.0);
+    }
+};
+
+// ---------------------------------------------------------------------------
 // Probe scenes (ours; scenes.cpp probe_scene builds the same with the
 // library's host API): one shading feature each.  The same literals, the same
 // std::cos / std::sin expressions and the same order of Add calls and of
@@ -459,6 +552,7 @@ static scene* make_scene(const std::string& name, double aspect) {
         return new probe_ref_scene(aspect, name.substr(6));
     if (name == "grouped") return new grouped_scene(aspect);
     if (name == "grouped_world") return new grouped_scene(aspect, true);
+    if (name == "ties") return new ties_ref_scene(aspect);
     if (name == "nested") return new nested_scene(aspect);
     if (name == "nested_plain") return new nested_scene(aspect, false);
     if (name == "cornell_box") return new cornell_box_scene(aspect);

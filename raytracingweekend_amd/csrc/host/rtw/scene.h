@@ -68,6 +68,19 @@ public:
     explicit grouped_scene(double aspect, bool extra = false);
 };
 
+// Test scenes for the equal-distance rule of hittable_list::hit (scenes.cpp):
+// "ties" is made of twins, primitives of identical geometry and different
+// material and normal, of every class and in every walk; "ties_axis" holds
+// stations where a sphere and a rect touch on an axis-parallel ray.
+class ties_scene : public scene {
+public:
+    explicit ties_scene(double aspect);
+};
+class ties_axis_scene : public scene {
+public:
+    explicit ties_axis_scene(double aspect);
+};
+
 // Test scene for image textures (not in the reference, whose scenes use
 // none): two images computed in code on every primitive kind (scenes.cpp).
 // `first`, when given, replaces the first image (nx * ny RGB texels).
@@ -93,8 +106,8 @@ public:
 
 // Builds a scene by name ("cornell_box", "random_balls", "dielectric",
 // "light_sample", "book2_final", "nested", "nested_plain", "textured",
-// "grouped", "grouped_world", and the test scenes "probe_<kind>" of
-// probe_scene);
+// "grouped", "grouped_world", "ties", "ties_axis", and the test scenes
+// "probe_<kind>" of probe_scene);
 // nullptr for an unknown name.
 std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect);
 

@@ -399,6 +399,156 @@ grouped_scene::grouped_scene(double aspect, bool extra) {
     cam = look(vec3(3.0, 3.5, 10.0), vec3(0.0, 0.6, 0.0), 35.0, aspect, 0.0, 10.0);
 }
 
+// ------------------------------------------------------------------ ties
+// Test scenes for the equal-distance rule of hittable_list::hit (a rect
+// accepts t == t_max and so the last rect among equals wins; a sphere needs
+// t < t_max, so the first sphere is kept; a rect beats a sphere either way).
+// Not in the reference; composed the same way in oracle/ref_harness.cpp.
+namespace {
+mat_ptr mirror() { return std::make_shared<metal>(vec3(0.9, 0.9, 0.9), 0.0); }
+std::shared_ptr<hittable> twin_mover(const vec3& c0, const vec3& c1, double r, mat_ptr m) {
+    auto ms = std::make_shared<moving_sphere>(c0, r, m);
+    movement_linear mv;
+    mv.center1 = c1;
+    mv.time0 = 0.0;
+    mv.time1 = 1.0;
+    ms->set_movement(mv);
+    return ms;
+}
+}  // namespace
+
+// "ties": twins -- two primitives of identical geometry, so that their t is
+// bit-identical on every ray -- under a gradient sky, without media or
+// lights.  Twins differ in material (a Lambertian colour against a mirror)
+// and, where the class allows, in normal (radius -r, the same radius^2; or
+// flip_normals), so the winner shows in the radiance, the traversal count
+// and RenderType::Normal.  Twenty-two world objects (a world BVH under
+// use_bvh); in list order, with the flat walk's runs:
+//   a  static sphere twins, centre y != 0 } one run of spheres that move
+//   c  twin y-only movers                 } along y or not at all
+//   d  a sphere, then its twin under translate(., 0); a sphere under
+//      translate(., 0), then its plain twin (x - 0 is exact: equal t bits in
+//      two different entries, one with ops)
+//   b  sphere twins with centre y == 0    } one plain run of spheres, movers
+//   c' twin x-movers                      } and rects
+//   e  coincident xy_rect twins and a third rect over a part of them
+//   f  a yz_rect, then its twin under rotate_y(., 0) (sin 0, cos 1: exact);
+//      an xz_rect under rotate_y(., 0), then its flipped twin
+//   g  a translated list of five sphere twin pairs (a group BVH of prim
+//      items; the order within a pair alternates)
+//   h  a translated list of five box twin pairs (a group BVH of box items);
+//      neighbouring boxes also share a part of a face
+//      (the BVH builder splits by centroid, so twins stay in one leaf of two
+//      items; g and h hold one glass triplet each, which it has to part)
+ties_scene::ties_scene(double aspect) {
+    using list = std::vector<std::shared_ptr<hittable>>;
+    const vec3 zero(0.0, 0.0, 0.0);
+    Add(std::make_shared<sphere>(vec3(0, -1000, 0), 1000.0, diffuse(0.5, 0.5, 0.5)));
+    // a
+    Add(std::make_shared<sphere>(vec3(-4.0, 0.6, 0.0), 0.6, diffuse(0.8, 0.2, 0.2)));
+    Add(std::make_shared<sphere>(vec3(-4.0, 0.6, 0.0), -0.6, mirror()));
+    // c
+    Add(twin_mover(vec3(-2.5, 0.5, 0.25), vec3(-2.5, 0.9, 0.25), 0.5, diffuse(0.2, 0.7, 0.3)));
+    Add(twin_mover(vec3(-2.5, 0.5, 0.25), vec3(-2.5, 0.9, 0.25), -0.5, mirror()));
+    // d
+    Add(std::make_shared<sphere>(vec3(-1.0, 0.6, 0.0), 0.6, diffuse(0.2, 0.3, 0.8)));
+    Add(std::make_shared<translate>(std::make_shared<sphere>(vec3(-1.0, 0.6, 0.0), -0.6, mirror()), zero));
+    Add(std::make_shared<translate>(std::make_shared<sphere>(vec3(0.5, 0.6, 0.0), 0.6, diffuse(0.8, 0.7, 0.2)), zero));
+    Add(std::make_shared<sphere>(vec3(0.5, 0.6, 0.0), -0.6, mirror()));
+    // b
+    Add(std::make_shared<sphere>(vec3(2.5, 0.0, 2.5), 0.7, diffuse(0.7, 0.3, 0.7)));
+    Add(std::make_shared<sphere>(vec3(2.5, 0.0, 2.5), -0.7, mirror()));
+    // c'
+    Add(twin_mover(vec3(-3.6, 0.4, 2.5), vec3(-3.3, 0.4, 2.5), 0.4, diffuse(0.3, 0.7, 0.7)));
+    Add(twin_mover(vec3(-3.6, 0.4, 2.5), vec3(-3.3, 0.4, 2.5), -0.4, mirror()));
+    // e
+    Add(std::make_shared<xy_rect>(1.5, 3.0, 0.0, 1.5, -0.5, diffuse(0.8, 0.5, 0.2)));
+    Add(std::make_shared<flip_normals>(std::make_shared<xy_rect>(1.5, 3.0, 0.0, 1.5, -0.5, mirror())));
+    Add(std::make_shared<xy_rect>(2.25, 3.5, 0.5, 2.0, -0.5, diffuse(0.2, 0.8, 0.5)));
+    // f
+    Add(std::make_shared<yz_rect>(0.0, 2.0, -1.0, 1.5, 4.0, diffuse(0.5, 0.2, 0.8)));
+    Add(std::make_shared<rotate_y>(
+        std::make_shared<flip_normals>(std::make_shared<yz_rect>(0.0, 2.0, -1.0, 1.5, 4.0, mirror())), 0.0));
+    Add(std::make_shared<rotate_y>(std::make_shared<xz_rect>(-1.0, 1.0, 4.5, 6.5, 0.2, diffuse(0.8, 0.8, 0.3)), 0.0));
+    Add(std::make_shared<flip_normals>(std::make_shared<xz_rect>(-1.0, 1.0, 4.5, 6.5, 0.2, mirror())));
+    // g
+    list balls;
+    for (int k = 0; k < 5; ++k) {
+        const vec3 c(-2.0 + k, 0.3, 0.0);
+        auto plain = std::make_shared<sphere>(c, 0.3, diffuse(0.3 + 0.1 * k, 0.6, 0.9 - 0.15 * k));
+        auto twin = std::make_shared<sphere>(c, -0.3, mirror());
+        if (k & 1)
+            balls.push_back(twin), balls.push_back(plain);
+        else
+            balls.push_back(plain), balls.push_back(twin);
+        // a third coincident sphere: three items of one centre part 1 + 2 into leaves of two
+        if (k == 2) balls.push_back(std::make_shared<sphere>(c, 0.3, std::make_shared<dielectric>(1.5)));
+    }
+    Add(std::make_shared<translate>(std::make_shared<hittable_list>(balls), vec3(0.0, 0.0, 2.0)));
+    // h
+    list crates;
+    for (int k = 0; k < 5; ++k) {
+        const vec3 p0(k, 0.0, 0.0), p1(k + 1.0, 0.3 + 0.05 * k, 0.6);
+        auto plain = std::make_shared<box>(p0, p1, diffuse(0.9 - 0.15 * k, 0.4, 0.2 + 0.15 * k));
+        auto twin = std::make_shared<flip_normals>(std::make_shared<box>(p0, p1, mirror()));
+        // a third coincident box, first in the list (the last one wins)
+        if (k == 2) crates.push_back(std::make_shared<box>(p0, p1, std::make_shared<dielectric>(1.5)));
+        if (k & 1)
+            crates.push_back(twin), crates.push_back(plain);
+        else
+            crates.push_back(plain), crates.push_back(twin);
+    }
+    Add(std::make_shared<translate>(std::make_shared<hittable_list>(crates), vec3(-2.5, 0.0, 3.2)));
+
+    cam = camera(vec3(0.0, 2.5, 10.0), vec3(0.0, 0.6, 0.0), vec3(0.0, 1.0, 0.0), 38.0, aspect, 0.0, 10.0, 0.0, 1.0);
+}
+
+// "ties_axis": stations at x = 10 k, each a sphere((10 k, 0, -5), 1) and an
+// xy_rect(10 k - 1, 10 k + 1, -1, 1, -4) that touches it at (10 k, 0, -4).
+// A camera at (10 k, 0, 0) whose every ray is (0, 0, -1) (lower_left
+// (10 k, 0, -1), horizontal = vertical = 0, no lens; the test's own
+// rtw_camera_desc) meets both at exactly t = 4 in small integers.  List
+// orders [sphere, rect], [rect, sphere], [rect, sphere, rect'] and, inside
+// one translated list, [rect, sphere, rect'] again; the last rect wins.
+// Station 4 is [rect, sphere] with a rect ten wide to one side, xy_rect(39,
+// 49, -1, 1, -4): its centre lies beside the sphere's, not in front of it, so
+// a BVH walk reaches the sphere first and the rect, earlier in the list,
+// second (in stations 0 to 3 the rect's box is the nearer one).  The
+// winner is flipped and emits (diffuse_light emits where dot(normal, ray) >
+// 0): its pixel is its emission, exactly, in either precision, and its Normal
+// colour (0.5, 0.5, 0).  The sphere's normal there and the other rect's are
+// (0, 0, 1): Normal colour (0.5, 0.5, 1), and Lambertian.  Filler balls bring
+// the world to sixteen objects (a world BVH).
+ties_axis_scene::ties_axis_scene(double aspect) {
+    using list = std::vector<std::shared_ptr<hittable>>;
+    auto glow = [](double r, double g, double b) { return std::make_shared<diffuse_light>(solid(r, g, b)); };
+    auto ball = [](double x, mat_ptr m) { return std::make_shared<sphere>(vec3(x, 0.0, -5.0), 1.0, m); };
+    auto wall = [](double x, mat_ptr m) { return std::make_shared<xy_rect>(x - 1.0, x + 1.0, -1.0, 1.0, -4.0, m); };
+    auto won = [&](double x, mat_ptr m) { return std::make_shared<flip_normals>(wall(x, m)); };
+    // station 0: [sphere, rect]
+    Add(ball(0.0, diffuse(0.8, 0.2, 0.2)));
+    Add(won(0.0, glow(0.5, 1.0, 0.25)));
+    // station 1: [rect, sphere]
+    Add(won(10.0, glow(1.0, 0.25, 0.5)));
+    Add(ball(10.0, diffuse(0.8, 0.8, 0.2)));
+    // station 2: [rect, sphere, rect']
+    Add(wall(20.0, diffuse(0.8, 0.2, 0.8)));
+    Add(ball(20.0, diffuse(0.2, 0.8, 0.8)));
+    Add(won(20.0, glow(0.25, 0.5, 1.0)));
+    // station 3: the same three inside one translated list
+    Add(std::make_shared<translate>(
+        std::make_shared<hittable_list>(list{wall(0.0, diffuse(0.1, 0.5, 0.9)), ball(0.0, diffuse(0.5, 0.9, 0.1)),
+                                             won(0.0, glow(2.0, 0.5, 0.125))}),
+        vec3(30.0, 0.0, 0.0)));
+    // station 4: [rect, sphere], the rect wide and to one side
+    Add(std::make_shared<flip_normals>(std::make_shared<xy_rect>(39.0, 49.0, -1.0, 1.0, -4.0, glow(0.125, 2.0, 1.0))));
+    Add(ball(40.0, diffuse(0.6, 0.6, 0.1)));
+    for (int k = 0; k < 6; ++k)
+        Add(std::make_shared<sphere>(vec3(5.0 + 10.0 * (k % 3), k < 3 ? 3.0 : -3.0, -6.0), 0.5,
+                                     diffuse(0.3 + 0.1 * k, 0.5, 0.7 - 0.1 * k)));
+    cam = look(vec3(15.0, 0.0, 30.0), vec3(15.0, 0.0, -5.0), 40.0, aspect, 0.0, 10.0);
+}
+
 // ---------------------------------------------------------------- probes
 // Test scenes for the converged fp32-vs-fp64 comparison: one shading feature
 // each, filling the frame, with bounded radiance (a gradient sky, or lights
@@ -578,6 +728,8 @@ std::unique_ptr<scene> make_builtin_scene(const std::string& name, double aspect
         return std::make_unique<probe_scene>(aspect, name.substr(6));
     if (name == "grouped") return std::make_unique<grouped_scene>(aspect);
     if (name == "grouped_world") return std::make_unique<grouped_scene>(aspect, true);
+    if (name == "ties") return std::make_unique<ties_scene>(aspect);
+    if (name == "ties_axis") return std::make_unique<ties_axis_scene>(aspect);
     if (name == "nested") return std::make_unique<nested_scene>(aspect);
     if (name == "nested_plain") return std::make_unique<nested_scene>(aspect, false);
     if (name == "cornell_box") return std::make_unique<cornell_box_scene>(aspect);

@@ -71,6 +71,15 @@ int validate_desc(const rtw_scene_desc* d) {
                                                      std::to_string(d->prims[p].entry) + " but lies in entry " +
                                                      std::to_string(owner[p]) + "'s range");
     }
+    // Prim ranges ascend with the entry index.  Among primitives hit at the
+    // same distance the reference decides by list position; the BVH walks
+    // decide by prim index (rtw_device.h better()), which is the list
+    // position only while a later entry's prims follow an earlier entry's.
+    for (int e = 1; e < d->n_entries; ++e)
+        if (d->entries[e].first_prim < d->entries[e - 1].first_prim + d->entries[e - 1].n_prims)
+            return rtw_fail(RTW_ERR_UNSUPPORTED, "entry " + std::to_string(e) + ": prim range lies before entry " +
+                                                     std::to_string(e - 1) +
+                                                     "'s (prim ranges must ascend with the entry index)");
     for (int m = 0; m < d->n_materials; ++m) {
         const rtw_material& M = d->materials[m];
         const bool tex = M.type == RTW_MAT_LAMBERTIAN || M.type == RTW_MAT_DIFFUSE_LIGHT || M.type == RTW_MAT_ISOTROPIC;

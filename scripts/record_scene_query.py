@@ -2,7 +2,8 @@
 """What rtw_scene_query reports (kernel, kernel_fast, bvh_lds_nodes,
 shade_lds_bytes) for every scene of tests/golden/scene_*.json but the probe
 scenes (scene_probe_*.json: their kernels are listed, with the renders that
-drive them, in profiles/probe_reference/kernels_by_case.txt), flat and with
+drive them, in profiles/probe_reference/kernels_by_case.txt) and the scene of
+coincident primitives (scene_ties.json: profiles/ties/kernels_by_case.txt), flat and with
 BVHs, under the environments that steer kernel selection: {}, RTW_MODE=wavefront
 and wavefront + RTW_SPLIT=1 in this process (read at every call), RTW_SORT=0
 and RTW_SORT=1 in one child process each (read once).  Prints one JSON
@@ -30,7 +31,7 @@ def query_all():
     out = {}
     for p in sorted((ROOT / "tests" / "golden").glob("scene_*.json")):
         name, aspect = p.stem[len("scene_"):], json.loads(p.read_text()).get("aspect")
-        if name.startswith("probe_"):
+        if name.startswith("probe_") or name == "ties":  # (younger than the recording; profiles/ties/ lists its kernels)
             continue
         for bvh in (False, True) if aspect else ():  # (this script's own output is no scene dump)
             ds = render.DeviceScene(render.SceneDesc(name, aspect, use_bvh=bvh))

@@ -105,6 +105,22 @@ class DescCopy:
         self._keep.append(nodes)
         return nodes
 
+    def own_prims(self):
+        """Replace the prim array with a private copy and return it."""
+        prims = (_abi.rtw_prim * self._d.n_prims)()
+        C.memmove(prims, self._d.prims, C.sizeof(prims))
+        self._d.prims = C.cast(prims, C.POINTER(_abi.rtw_prim))
+        self._keep.append(prims)
+        return prims
+
+    def own_entries(self):
+        """Replace the entry array with a private copy and return it."""
+        entries = (_abi.rtw_entry * self._d.n_entries)()
+        C.memmove(entries, self._d.entries, C.sizeof(entries))
+        self._d.entries = C.cast(entries, C.POINTER(_abi.rtw_entry))
+        self._keep.append(entries)
+        return entries
+
     def set_world_bvh(self, nodes, items, root):
         """Install a world BVH of the test's own (a desc without BVHs)."""
         assert self._d.n_bvh_nodes == 0 and self._d.n_bvh_items == 0

@@ -8,7 +8,8 @@
 //      ops, BVH links, visit program, null arrays -- and handed to
 //      validate_desc, which must refuse or accept them without touching
 //      memory it does not own; and Book 2 with one group BVH node turned
-//      into a leaf of 17 items (refused) and of 16 (accepted);
+//      into a leaf of 17 items (refused) and of 16 (accepted); prim ranges
+//      that do not ascend with the entry index (refused);
 //   3. refused graphs (a bvh_node over a medium, unknown subclasses, nulls);
 //   4. the oracle rendering each valid desc, finalize, the PPM writer;
 //   5. the header API's evaluating half (hit / scatter / get_ray / pdfs) over
@@ -188,7 +189,7 @@ vec3 color(const ray& r, const scene& s, int depth) {
 int main() {
     std::mt19937 g(12345);
     const char* names[] = {"cornell_box", "random_balls", "dielectric", "light_sample", "book2_final", "nested",
-                           "nested_plain", "grouped", "grouped_world"};
+                           "nested_plain", "grouped", "grouped_world", "ties", "ties_axis"};
     char ppm[] = "/tmp/rtw_sanitize_XXXXXX";
     const int fd = mkstemp(ppm);
     CHECK(fd >= 0);
@@ -249,6 +250,23 @@ int main() {
             o.nodes[pick].left = first[pick], o.nodes[pick].right = -1, o.nodes[pick].count = count;
             CHECK(validate_desc(&o.d) == (count > 16 ? RTW_ERR_UNSUPPORTED : RTW_OK));
         }
+        rtw_scene_desc_free(d);
+    }
+    // prim ranges that do not ascend with the entry index (two entries of one
+    // prim each, their ranges exchanged: the same list, but prim index order is
+    // no longer list order, which decides hits at equal distance): refused
+    for (int bvh = 0; bvh < 2; ++bvh) {
+        rtw_scene_desc* d = nullptr;
+        CHECK(rtw_scene_builtin("ties", 1.5, bvh, &d) == RTW_OK && d);
+        owned_desc o(*d);
+        rtw_entry &a = o.entries[5], &b = o.entries[6];
+        CHECK(a.n_prims == 1 && b.n_prims == 1 && a.n_ops == 0 && b.n_ops == 1);
+        std::swap(o.prims[a.first_prim], o.prims[b.first_prim]);
+        std::swap(a.first_prim, b.first_prim);
+        o.prims[a.first_prim].entry = 5, o.prims[b.first_prim].entry = 6;
+        CHECK(validate_desc(&o.d) == RTW_ERR_UNSUPPORTED);
+        CHECK(std::string(rtw_last_error()).find("prim ranges must ascend") != std::string::npos);
+        CHECK(validate_desc(d) == RTW_OK);
         rtw_scene_desc_free(d);
     }
     // refused graphs

@@ -43,6 +43,9 @@ CASES = [
     # group BVHs without media: k_fast<F_GBVH> and k_fast<F_WBVH | F_GBVH>
     ("grouped", 96, 64, 16, 50, True),
     ("grouped_world", 96, 64, 16, 50, True),
+    # coincident primitives (hits at equal distance), list walks and BVHs
+    ("ties", 96, 64, 16, 50, False),
+    ("ties", 96, 64, 16, 50, True),
 ]
 
 

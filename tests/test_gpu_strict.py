@@ -46,6 +46,8 @@ PROBE_KINDS = ["rect_light", "sphere_light", "far_sphere_light", "default_light"
                "motion", "textures"]
 CASES += [(f"probe_{kind}", 32, 24, 4, 50, False) for kind in PROBE_KINDS]
 CASES += [(f"probe_{kind}", 32, 24, 4, 50, True) for kind in ("medium", "motion", "default_light")]
+# coincident primitives: every equal-distance decision is the list walk's
+CASES += [("ties", 48, 32, 4, 50, False), ("ties", 48, 32, 4, 50, True)]
 
 
 @pytest.fixture(scope="module")

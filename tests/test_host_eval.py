@@ -62,6 +62,7 @@ def test_host_color_matches_reference_render(host_render, tmp_path, case):
                                              ("light_sample", 32, 16, 2), ("book2_final", 16, 16, 2),
                                              ("nested", 24, 24, 2), ("grouped", 32, 24, 2),
                                              ("grouped_world", 32, 24, 2), ("normal:grouped_world", 32, 24, 2),
+                                             ("ties", 48, 32, 2), ("normal:ties", 48, 32, 2),
                                              *[(f"probe_{kind}", 32, 24, 2) for kind in PROBE_KINDS]])
 def test_host_bvh_equals_flat_list(host_render, tmp_path, scene, nx, ny, spp):
     """bvh_node::hit (median-split tree, nearest-first walk, then the list

@@ -15,6 +15,8 @@ from raytracingweekend_amd import _abi
 
 GOLD = Path(__file__).resolve().parent / "golden"
 SCENES = ["cornell_box", "random_balls", "dielectric", "light_sample", "book2_final"]
+# the scene of coincident primitives, composed from the reference's classes in oracle/ref_harness.cpp
+SCENES += ["ties"]
 # the probe scenes, composed from the reference's classes in oracle/ref_harness.cpp
 PROBES = ["probe_" + kind for kind in ("rect_light", "sphere_light", "far_sphere_light", "default_light", "glass",
                                        "metal", "medium", "motion", "textures")]
