@@ -218,6 +218,21 @@ DENOISE_SIGNATURES = {
     "rtw_finalize_canvas_mean_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 
+RTW_WINDOW_RADIUS_MAX = 16  # include/rtw_adaptive_window.h
+
+# the functions of include/rtw_adaptive_window.h (its own header, its own table)
+ADAPTIVE_WINDOW_SIGNATURES = {
+    "rtw_adaptive_select_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                             C.c_double, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+                                             C.POINTER(C.c_uint64)]),
+    "rtw_adaptive_select_window_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                    C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_int,
+                                                    C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rtw_render_adaptive_window": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera_desc), C.POINTER(rtw_render_params),
+                                             C.POINTER(rtw_adaptive_params), C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(rtw_adaptive_result), C.POINTER(rtw_stats)]),
+}
+
 _lib = None
 
 
@@ -239,7 +254,7 @@ def load_library(path) -> C.CDLL:
                            f"`python -m raytracingweekend_amd.build` (there is no CPU fallback)")
     L = C.CDLL(str(path))
     for name, (res, args) in [*SIGNATURES.items(), *NOISE_SIGNATURES.items(), *ADAPTIVE_SIGNATURES.items(),
-                              *DENOISE_SIGNATURES.items()]:
+                              *DENOISE_SIGNATURES.items(), *ADAPTIVE_WINDOW_SIGNATURES.items()]:
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

@@ -43,6 +43,7 @@
 #include "rtw_fast.h"
 #include "rtw_queue.h"
 #include "host/adaptive.h"
+#include "host/adaptive_window.h"
 #include "host/denoise.h"
 #include "host/render_plan.h"
 #include "host/rtw_host_util.h"
@@ -1908,7 +1909,10 @@ __device__ __forceinline__ bool select_flag(const select_args& A, uint64_t p) {
     const double s2[3] = {A.accum_sq[3 * p], A.accum_sq[3 * p + 1], A.accum_sq[3 * p + 2]};
     return rtw_pixel_active(s1, s2, A.cnt[p], A.floor3, A.target_rel, A.max_count);
 }
-__global__ __launch_bounds__(kBlock) void k_select_count(select_args A, uint32_t* __restrict__ block_counts) {
+// (the two bodies are templates over the flag's arguments: select_args here,
+// window_args of rtw_adaptive_window.h below)
+template <class Args>
+__device__ __forceinline__ void select_count_body(const Args& A, uint32_t* __restrict__ block_counts) {
     __shared__ uint32_t s_wave[kWaves];
     const uint64_t lo = blockIdx.x * A.chunk;
     uint32_t mine = 0;
@@ -1916,6 +1920,25 @@ __global__ __launch_bounds__(kBlock) void k_select_count(select_args A, uint32_t
     uint32_t total;
     block_scan(mine, s_wave, total);
     if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+}
+template <class Args>
+__device__ __forceinline__ void select_scatter_body(const Args& A, const uint32_t* __restrict__ offsets,
+                                                    uint32_t* __restrict__ active) {
+    __shared__ uint32_t s_wave[kWaves];
+    const uint64_t lo = blockIdx.x * A.chunk;
+    uint32_t base = offsets[blockIdx.x];
+    for (uint64_t t = 0; t < A.chunk; t += kBlock) {
+        const uint64_t p = lo + t + threadIdx.x;
+        const bool on = select_flag(A, p);
+        uint32_t total;
+        const uint32_t rank = block_rank(on, s_wave, total);
+        if (on) active[base + rank] = (uint32_t)p;
+        base += total;
+        __syncthreads();  // (s_wave is rewritten by the next tile)
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_select_count(select_args A, uint32_t* __restrict__ block_counts) {
+    select_count_body(A, block_counts);
 }
 // one block: offsets[b] = block_counts[0] + ... + block_counts[b - 1], offsets[n_blocks] = the total
 __global__ __launch_bounds__(kBlock) void k_select_scan(const uint32_t* __restrict__ block_counts, uint32_t n_blocks,
@@ -1941,18 +1964,95 @@ __global__ __launch_bounds__(kBlock) void k_select_scan(const uint32_t* __restri
 }
 __global__ __launch_bounds__(kBlock) void k_select_scatter(select_args A, const uint32_t* __restrict__ offsets,
                                                            uint32_t* __restrict__ active) {
-    __shared__ uint32_t s_wave[kWaves];
-    const uint64_t lo = blockIdx.x * A.chunk;
-    uint32_t base = offsets[blockIdx.x];
-    for (uint64_t t = 0; t < A.chunk; t += kBlock) {
-        const uint64_t p = lo + t + threadIdx.x;
-        const bool on = select_flag(A, p);
-        uint32_t total;
-        const uint32_t rank = block_rank(on, s_wave, total);
-        if (on) active[base + rank] = (uint32_t)p;
-        base += total;
-        __syncthreads();  // (s_wave is rewritten by the next tile)
+    select_scatter_body(A, offsets, active);
+}
+
+// rtw_adaptive_select_window_device (rtw_adaptive_window.h): the window rule
+// on bit planes.  A plane holds one bit per pixel, rows padded to
+// W = ceil(nx / 64) words so that a word never straddles rows: bit k of word
+// j * W + w is pixel (w * 64 + k, j); the bits beyond nx are 0.
+//   k_source_bits   a wave owns one word: each lane evaluates "finite" and
+//                   SOURCE (adaptive_window.h, the host's functions) of its
+//                   pixel -- the only place the fp64 divisions and square
+//                   roots of rtw_pixel_rel run, once per pixel -- and a ballot
+//                   makes the two words, which lane 0 stores.
+//   k_dilate_bits   a thread owns one word of the output plane: the OR over
+//                   the rows j - r .. j + r that exist of the source word and
+//                   its two neighbours, then the OR of the shifts by -r .. r
+//                   with the carries from the neighbours (r <= 16 needs no
+//                   word further away), and "finite" ANDed in: bit p of the
+//                   result is "p is finite and a source lies in its window".
+//   k_window_count / k_window_scatter   k_select_count / k_select_scatter with
+//                   that bit and the counts' range as the flag; k_select_scan
+//                   between them as it is.
+// Every word of the three planes is written before it is read, so scratch
+// reused from an earlier call needs no clearing.  No atomics; the grids depend
+// on (nx, ny) only.
+constexpr unsigned kBitsMaxGrid = 4096;
+struct window_planes {
+    uint64_t *src, *fin, *out;
+    uint32_t nx, ny, W;
+    RTW_HD uint64_t words() const { return (uint64_t)ny * W; }
+};
+__global__ __launch_bounds__(kBlock) void k_source_bits(const double* __restrict__ accum,
+                                                        const double* __restrict__ accum_sq,
+                                                        const uint32_t* __restrict__ counts, window_planes P,
+                                                        double floor3, double target_rel) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t words = P.words();
+    // (the loop's condition is the same for a wave's 64 lanes: the ballots see them all)
+    for (uint64_t word = blockIdx.x * (uint64_t)kWaves + (threadIdx.x >> 6); word < words;
+         word += (uint64_t)gridDim.x * kWaves) {
+        const uint32_t j = (uint32_t)(word / P.W), i = (uint32_t)(word % P.W) * 64u + lane;
+        bool fin = false, src = false;
+        if (i < P.nx) {
+            const uint64_t p = (uint64_t)j * P.nx + i;
+            const double s1[3] = {accum[3 * p], accum[3 * p + 1], accum[3 * p + 2]};
+            const double s2[3] = {accum_sq[3 * p], accum_sq[3 * p + 1], accum_sq[3 * p + 2]};
+            fin = rtw_pixel_finite(s1, s2);
+            src = rtw_pixel_source(s1, s2, fin, counts[p], floor3, target_rel);
+        }
+        const unsigned long long mf = __ballot(fin), ms = __ballot(src);
+        if (lane == 0) P.fin[word] = mf, P.src[word] = ms;
     }
+}
+__global__ __launch_bounds__(kBlock) void k_dilate_bits(window_planes P, int radius) {
+    const uint64_t words = P.words();
+    for (uint64_t word = blockIdx.x * (uint64_t)kBlock + threadIdx.x; word < words;
+         word += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t j = (uint32_t)(word / P.W), w = (uint32_t)(word % P.W);
+        const uint32_t j0 = j > (uint32_t)radius ? j - (uint32_t)radius : 0u;
+        const uint32_t j1 = j + (uint32_t)radius < P.ny - 1 ? j + (uint32_t)radius : P.ny - 1;
+        uint64_t c = 0, l = 0, r = 0;  // the word's column, the one before and the one after, ORed over the rows
+        for (uint32_t jj = j0; jj <= j1; ++jj) {
+            const uint64_t* row = P.src + (uint64_t)jj * P.W;
+            c |= row[w];
+            if (w > 0) l |= row[w - 1];
+            if (w + 1 < P.W) r |= row[w + 1];
+        }
+        uint64_t d = c;
+        for (int s = 1; s <= radius; ++s) d |= (c << s) | (l >> (64 - s)) | (c >> s) | (r << (64 - s));
+        P.out[word] = d & P.fin[word];
+    }
+}
+struct window_args {
+    const uint64_t* bits;  // window_planes::out
+    const uint32_t* counts;
+    uint64_t npix, chunk;
+    uint32_t nx, W, min_count, max_count;
+};
+__device__ __forceinline__ bool select_flag(const window_args& A, uint64_t p) {
+    if (p >= A.npix) return false;
+    const uint32_t j = (uint32_t)p / A.nx, i = (uint32_t)p - j * A.nx;  // (npix < 2^32)
+    const bool bit = (A.bits[(uint64_t)j * A.W + (i >> 6)] >> (i & 63u)) & 1u;
+    return rtw_pixel_eligible(bit, A.counts[p], A.min_count, A.max_count);
+}
+__global__ __launch_bounds__(kBlock) void k_window_count(window_args A, uint32_t* __restrict__ block_counts) {
+    select_count_body(A, block_counts);
+}
+__global__ __launch_bounds__(kBlock) void k_window_scatter(window_args A, const uint32_t* __restrict__ offsets,
+                                                           uint32_t* __restrict__ active) {
+    select_scatter_body(A, offsets, active);
 }
 
 // ---- rtw_denoise.h ------------------------------------------------------------
@@ -2189,6 +2289,7 @@ struct handle_t {
     dev_buf alist;    // the device copy of a host pixel list; the adaptive loop's list
     dev_buf counts;   // the device copy of a host counts buffer; the adaptive loop's counts
     dev_buf sel;      // rtw_adaptive_select_device: per-block counts, their prefix, the list check's flag
+    dev_buf wbits;    // rtw_adaptive_select_window_device: the three bit planes (window_planes)
     // rtw_denoise.h
     dev_buf features;     // the device copy of a host feature buffer
     dev_buf dn_state[2];  // rtw_denoise_device: the iteration state, ping-pong (rtw_dn_state)
@@ -3354,6 +3455,56 @@ extern "C" int rtw_adaptive_select_device(void* handle, const double* accum, con
     return RTW_OK;
 }
 
+// rtw_adaptive_window.h's select: the two bit-plane kernels, then the count,
+// scan and scatter over the window bit; *n_out as launch_select leaves it.
+static int launch_select_window(handle_t* h, const double* accum, const double* accum_sq, const uint32_t* counts, int nx,
+                                int ny, double floor, double target_rel, uint32_t min_count, uint32_t max_count,
+                                int radius, uint32_t* active_dev, uint32_t* n_out) {
+    const uint64_t npix = (uint64_t)nx * (uint64_t)ny;
+    window_planes P{nullptr, nullptr, nullptr, (uint32_t)nx, (uint32_t)ny, ((uint32_t)nx + 63u) / 64u};
+    const uint64_t words = P.words();
+    if (int rc = h->sel.ensure(sizeof(uint32_t) * (2 * kSelectMaxGrid + 2))) return rc;
+    if (int rc = h->wbits.ensure(3 * words * sizeof(uint64_t))) return rc;
+    P.src = static_cast<uint64_t*>(h->wbits.p), P.fin = P.src + words, P.out = P.fin + words;
+    uint32_t* block_counts = static_cast<uint32_t*>(h->sel.p) + 1;  // ([0]: the list check's flag)
+    uint32_t* offsets = block_counts + kSelectMaxGrid;
+    const unsigned grid = select_grid(npix);
+    const unsigned grid_src = (unsigned)std::min<uint64_t>((words + kWaves - 1) / kWaves, kBitsMaxGrid);
+    const unsigned grid_dil = (unsigned)std::min<uint64_t>((words + kBlock - 1) / kBlock, kBitsMaxGrid);
+    const window_args A{P.out, counts, npix, select_chunk(npix), P.nx, P.W, min_count, max_count};
+    hipStream_t st = h->stream;
+    hipLaunchKernelGGL(k_source_bits, dim3(grid_src), dim3(kBlock), 0, st, accum, accum_sq, counts, P, 3.0 * floor,
+                       target_rel);
+    hipLaunchKernelGGL(k_dilate_bits, dim3(grid_dil), dim3(kBlock), 0, st, P, radius);
+    hipLaunchKernelGGL(k_window_count, dim3(grid), dim3(kBlock), 0, st, A, block_counts);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(kBlock), 0, st, block_counts, (uint32_t)grid, offsets);
+    hipLaunchKernelGGL(k_window_scatter, dim3(grid), dim3(kBlock), 0, st, A, offsets, active_dev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(n_out, offsets + grid, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return RTW_OK;
+}
+
+extern "C" int rtw_adaptive_select_window_device(void* handle, const double* accum, const double* accum_sq,
+                                                 const uint32_t* counts, int nx, int ny, double floor,
+                                                 double target_rel, uint32_t min_count, uint32_t max_count, int radius,
+                                                 uint32_t* active_dev, uint64_t* n_active_host) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    const char* const what = "rtw_adaptive_select_window_device";
+    if (!h) return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": null scene handle");
+    if (int rc = rtw_adaptive_window_check_select(what, accum, accum_sq, counts, nx, ny, floor, target_rel, min_count,
+                                                  max_count, radius, active_dev, n_active_host))
+        return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = check_handle_ptrs(h, what, {accum, accum_sq, counts, active_dev})) return rc;
+    uint32_t n = 0;
+    if (int rc = launch_select_window(h, accum, accum_sq, counts, nx, ny, floor, target_rel, min_count, max_count,
+                                      radius, active_dev, &n))
+        return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *n_active_host = n;
+    return RTW_OK;
+}
+
 extern "C" int rtw_noise_estimate_counts_device(void* handle, const double* accum, const double* accum_sq,
                                                 const uint32_t* counts, int nx, int ny, double floor,
                                                 double* stderr_dev, rtw_noise_summary* out) {
@@ -3389,16 +3540,19 @@ static void add_stats(rtw_stats& t, const rtw_stats& s) {
 // the rounds are this file's own render, select and estimate on device
 // buffers -- the caller's, or the handle's when the caller's are host memory
 // (copied out once at the end).
-extern "C" int rtw_render_adaptive(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
-                                   const rtw_adaptive_params* ap, double* accum_rgb, double* accum_sq_rgb,
-                                   uint32_t* counts, rtw_adaptive_result* out_result, rtw_stats* out_stats) {
+// One body for both entry points: radius < 0 is rtw_render_adaptive (a later
+// round selects with launch_select), radius >= 0 rtw_render_adaptive_window
+// (launch_select_window with min_count = done).
+static int adaptive_loop(const char* what, void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                         const rtw_adaptive_params* ap, int radius, double* accum_rgb, double* accum_sq_rgb,
+                         uint32_t* counts, rtw_adaptive_result* out_result, rtw_stats* out_stats) {
     handle_t* h = static_cast<handle_t*>(handle);
-    const char* const what = "rtw_render_adaptive";
     if (!h || !camera || !prm || !accum_rgb || !accum_sq_rgb || !counts)
         return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": null argument");
     if (int rc = rtw_adaptive_check_params(what, ap)) return rc;
     if (RTW_STRICT_RADIANCE)
-        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build renders whole images only (rtw_render_adaptive)");
+        return rtw_fail(RTW_ERR_UNSUPPORTED,
+                        std::string("the strict-radiance build renders whole images only (") + what + ")");
     if (prm->nx <= 0 || prm->ny <= 0 || (uint64_t)prm->nx * (uint64_t)prm->ny >= (1ull << 31))
         return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": bad image size");
     const uint64_t npix = (uint64_t)prm->nx * (uint64_t)prm->ny;
@@ -3445,8 +3599,11 @@ extern "C" int rtw_render_adaptive(void* handle, const rtw_camera_desc* camera, 
             HIPCHK(hipGetLastError());
         } else {
             uint32_t n = 0;
-            if (int rc = launch_select(h, a_dev, q_dev, c_dev, npix, ap->floor, ap->target_rel, (uint32_t)ap->max_spp,
-                                       list, &n))
+            if (int rc = radius < 0 ? launch_select(h, a_dev, q_dev, c_dev, npix, ap->floor, ap->target_rel,
+                                                    (uint32_t)ap->max_spp, list, &n)
+                                    : launch_select_window(h, a_dev, q_dev, c_dev, prm->nx, prm->ny, ap->floor,
+                                                           ap->target_rel, (uint32_t)done, (uint32_t)ap->max_spp,
+                                                           radius, list, &n))
                 return rc;
             HIPCHK(hipStreamSynchronize(st));
             if (n == 0) break;
@@ -3484,6 +3641,23 @@ extern "C" int rtw_render_adaptive(void* handle, const rtw_camera_desc* camera, 
     if (out_result) *out_result = res;
     if (out_stats) *out_stats = total;
     return RTW_OK;
+}
+
+extern "C" int rtw_render_adaptive(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                                   const rtw_adaptive_params* ap, double* accum_rgb, double* accum_sq_rgb,
+                                   uint32_t* counts, rtw_adaptive_result* out_result, rtw_stats* out_stats) {
+    return adaptive_loop("rtw_render_adaptive", handle, camera, prm, ap, -1, accum_rgb, accum_sq_rgb, counts,
+                         out_result, out_stats);
+}
+
+// rtw_adaptive_window.h
+extern "C" int rtw_render_adaptive_window(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                                          const rtw_adaptive_params* ap, int radius, double* accum_rgb,
+                                          double* accum_sq_rgb, uint32_t* counts, rtw_adaptive_result* out_result,
+                                          rtw_stats* out_stats) {
+    const char* const what = "rtw_render_adaptive_window";
+    if (int rc = rtw_adaptive_window_check_radius(what, radius)) return rc;
+    return adaptive_loop(what, handle, camera, prm, ap, radius, accum_rgb, accum_sq_rgb, counts, out_result, out_stats);
 }
 
 // ======================================================================

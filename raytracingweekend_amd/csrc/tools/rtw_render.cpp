@@ -7,7 +7,8 @@
 //              [--depth 100] [--seed 0] [--bvh] [--device 0] [--gpus 1]
 //              [--precision fp64|fp32] [--out out.ppm] [--image FILE.ppm]
 //              [--noise] [--noise-target X [--noise-batch 8] [--noise-floor 0.01]]
-//              [--adaptive X [--min-spp 16] [--noise-batch B] [--noise-floor 0.01]]
+//              [--adaptive X [--min-spp 16] [--noise-batch B] [--noise-floor 0.01]
+//                            [--adaptive-window R]]
 //              [--denoise [--denoise-iterations 5]]
 //
 // --noise renders through rtw_render_accumulate_moments (rtw_noise.h) and
@@ -21,6 +22,9 @@
 // many as are done so far) of the pixels whose relative standard error is
 // still above X, with --spp as the most a pixel takes; the canvas divides
 // every pixel's sum by its own sample count.  One GPU only.
+// --adaptive-window R (0..16, default 0) keeps a pixel sampling while any pixel
+// within R pixels of it is still above X (rtw_render_adaptive_window,
+// rtw_adaptive_window.h).
 //
 // --denoise filters the image before the canvas step (rtw_denoise.h): the
 // render keeps second moments, rtw_render_features adds the first-hit features
@@ -49,6 +53,7 @@
 #include "rtw/scene.h"
 #include "rtw_gpu.h"
 #include "rtw_adaptive.h"
+#include "rtw_adaptive_window.h"
 #include "rtw_denoise.h"
 #include "rtw_noise.h"
 
@@ -61,6 +66,8 @@ int main(int argc, char** argv) {
     int noise_batch = 8, min_spp = 16;
     bool adaptive = false, batch_given = false;
     double adaptive_target = 0.0;
+    int adaptive_window = 0;
+    bool window_given = false;
     bool denoise = false;
     int denoise_iterations = -1;  // (not given: the library's default)
     for (int i = 1; i < argc; ++i) {
@@ -87,6 +94,7 @@ int main(int argc, char** argv) {
         else if (a == "--noise-target") noise_target = std::atof(next()), noise = to_target = true;
         else if (a == "--noise-batch") noise_batch = std::atoi(next()), batch_given = true;
         else if (a == "--adaptive") adaptive_target = std::atof(next()), adaptive = true;
+        else if (a == "--adaptive-window") adaptive_window = std::atoi(next()), window_given = true;
         else if (a == "--min-spp") min_spp = std::atoi(next());
         else if (a == "--noise-floor") noise_floor = std::atof(next());
         else if (a == "--denoise") denoise = true;
@@ -123,6 +131,11 @@ int main(int argc, char** argv) {
                      !(noise_floor > 0.0))) {
         std::fprintf(stderr, "--adaptive needs a target >= 0, --min-spp >= 2, --spp >= --min-spp, --noise-batch >= 1, "
                              "--noise-floor > 0\n");
+        return 2;
+    }
+
+    if (window_given && (!adaptive || adaptive_window < 0 || adaptive_window > RTW_WINDOW_RADIUS_MAX)) {
+        std::fprintf(stderr, "--adaptive-window needs --adaptive and a radius in [0, %d]\n", RTW_WINDOW_RADIUS_MAX);
         return 2;
     }
 
@@ -189,7 +202,12 @@ int main(int argc, char** argv) {
         std::memset(&ap, 0, sizeof ap);
         ap.target_rel = adaptive_target, ap.floor = noise_floor, ap.min_spp = min_spp, ap.max_spp = spp;
         ap.batch = batch_given ? noise_batch : 0;
-        if (rtw_render_adaptive(h[0], &cam, &p, &ap, accum.data(), accum_sq.data(), counts.data(), &ar, &st) != RTW_OK) {
+        const int rc = adaptive_window
+                           ? rtw_render_adaptive_window(h[0], &cam, &p, &ap, adaptive_window, accum.data(),
+                                                        accum_sq.data(), counts.data(), &ar, &st)
+                           : rtw_render_adaptive(h[0], &cam, &p, &ap, accum.data(), accum_sq.data(), counts.data(), &ar,
+                                                 &st);
+        if (rc != RTW_OK) {
             std::fprintf(stderr, "render: %s\n", rtw_last_error());
             return 1;
         }
@@ -261,10 +279,13 @@ int main(int argc, char** argv) {
     if (noise)
         std::printf("Noise: spp %d of %d  mean_rel %.6e  max_rel %.6e  rms_stderr %.6e\n", spp_done, spp,
                     ns.mean_rel, ns.max_rel, ns.rms_stderr);
-    if (adaptive)
-        std::printf("Adaptive: rounds %u  samples %llu of %llu  mean_rel %.6e  max_rel %.6e  at_max %llu\n", ar.rounds,
+    if (adaptive) {
+        std::printf("Adaptive: rounds %u  samples %llu of %llu  mean_rel %.6e  max_rel %.6e  at_max %llu", ar.rounds,
                     (unsigned long long)ar.samples, (unsigned long long)nx * ny * spp, ar.final.mean_rel,
                     ar.final.max_rel, (unsigned long long)ar.pixels_at_max);
+        if (adaptive_window) std::printf("  window %d", adaptive_window);
+        std::printf("\n");
+    }
     if (denoise) std::printf("Denoise: iterations %d  %.3f ms\n", dp.iterations, denoise_ms);
     for (void* x : h) rtw_scene_free(x);
     if (gpus > 1) rtw_release_communicators();

@@ -243,6 +243,26 @@ class DeviceScene:
               "rtw_adaptive_select_device")
         return out[:n.value]
 
+    def select_active_window(self, accum, accum_sq, counts, nx: int, ny: int, *, target_rel: float, max_count: int,
+                             radius: int, min_count: int = 0, floor: float = 1e-2):
+        """The ascending list of the window-active pixels
+        (rtw_adaptive_window.h): torch tensors on this device go through
+        rtw_adaptive_select_window_device and give an int32 tensor, numpy
+        arrays through the host function, render.select_active_window."""
+        if isinstance(accum, np.ndarray):
+            return select_active_window(accum, accum_sq, counts, nx, ny, target_rel=target_rel, max_count=max_count,
+                                        radius=radius, min_count=min_count, floor=floor)
+        import torch
+        ptr, ptr_sq, _ = self._moment_buffers(accum, accum_sq, nx, ny)
+        ptr_counts = self._u32_ptr(counts, nx * ny, "counts", True)
+        out = torch.empty(nx * ny, dtype=torch.int32, device=accum.device)
+        torch.cuda.synchronize(accum.device)
+        n = C.c_uint64()
+        check(lib().rtw_adaptive_select_window_device(self.handle, ptr, ptr_sq, ptr_counts, nx, ny, floor, target_rel,
+                                                      min_count, max_count, radius, C.c_void_p(out.data_ptr()),
+                                                      C.byref(n)), "rtw_adaptive_select_window_device")
+        return out[:n.value]
+
     def noise_estimate_counts(self, accum, accum_sq, counts, nx: int, ny: int, floor: float = 1e-2,
                               want_stderr: bool = True):
         """noise_estimate with a per-pixel sample count (rtw_noise_estimate_counts
@@ -582,6 +602,22 @@ def select_active(accum, accum_sq, counts, nx: int, ny: int, *, target_rel: floa
     return out[:n.value].copy()
 
 
+def select_active_window(accum, accum_sq, counts, nx: int, ny: int, *, target_rel: float, max_count: int, radius: int,
+                         min_count: int = 0, floor: float = 1e-2) -> np.ndarray:
+    """rtw_adaptive_select_window on the host: the ascending uint32 list of the
+    pixels with min_count <= counts < max_count and finite moments in whose
+    clipped (2*radius+1)^2 window some pixel is a source: finite, and
+    counts < 2 or rel > target_rel (include/rtw_adaptive_window.h)."""
+    a, q, c = _moments_counts(accum, accum_sq, counts, nx, ny)
+    out = np.empty(nx * ny, dtype=np.uint32)
+    n = C.c_uint64()
+    check(lib().rtw_adaptive_select_window(a.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p),
+                                           c.ctypes.data_as(C.c_void_p), nx, ny, floor, target_rel, min_count,
+                                           max_count, radius, out.ctypes.data_as(C.c_void_p), C.byref(n)),
+          "rtw_adaptive_select_window")
+    return out[:n.value].copy()
+
+
 def noise_estimate_counts(accum, accum_sq, counts, nx: int, ny: int, floor: float = 1e-2, want_stderr: bool = True):
     """rtw_noise_estimate_counts on the host: noise_estimate with each pixel's
     own sample count; pixels with fewer than two samples are left out (counted
@@ -626,13 +662,18 @@ def adaptive_schedule(min_spp: int, max_spp: int, batch: int = 0):
 def render_adaptive(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: int = 0, *, target_rel: float,
                     min_spp: int = 16, batch: int = 0, floor: float = 1e-2, precision: str = "fp64",
                     device_buffers: bool = False, camera=None, denoise: bool = False,
-                    denoise_args: Optional[dict] = None) -> dict:
+                    denoise_args: Optional[dict] = None, window: int = 0) -> dict:
     """Adaptive per-pixel sampling, the library's loop (rtw_render_adaptive):
     [0, min_spp) of every pixel, then rounds of `batch` samples (0: doubling)
     of the pixels whose relative standard error is still above target_rel,
     until none is or max_spp samples are done.  A pixel stopped on the variance
     of its own samples is biased low where it is dark and heavy-tailed: that
     is what min_spp is for (include/rtw_adaptive.h).
+
+    window=R > 0 (at most 16) runs rtw_render_adaptive_window instead: a pixel
+    keeps sampling while any pixel within R pixels of it is still above
+    target_rel, which lessens that bias at the cost of more samples
+    (include/rtw_adaptive_window.h); 0 is rtw_render_adaptive itself.
 
     Returns a dict: accum, accum_sq (float64), counts (uint32 array, or int32
     tensor with device_buffers), rounds, samples, pixels_at_max, summary
@@ -645,6 +686,8 @@ def render_adaptive(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: in
     dict gains features, feature_spp and denoised (the linear mean; finalize
     it with ds.finalize_mean)."""
     ap = _adaptive_params(target_rel, floor, min_spp, max_spp, batch)
+    if not 0 <= window <= _abi.RTW_WINDOW_RADIUS_MAX:
+        raise ValueError(f"window must lie in [0, {_abi.RTW_WINDOW_RADIUS_MAX}]")
     if device_buffers:
         import torch
         accum = torch.zeros(nx * ny * 3, dtype=torch.float64, device=f"cuda:{ds.device}")
@@ -661,8 +704,12 @@ def render_adaptive(ds, nx: int, ny: int, max_spp: int, max_depth: int, seed: in
                                  accum_on_device=int(device_buffers), precision=_precision(precision))
     res, st = _abi.rtw_adaptive_result(), _abi.rtw_stats()
     cam = camera if camera is not None else ds.scene.camera
-    check(lib().rtw_render_adaptive(ds.handle, C.byref(cam), C.byref(prm), C.byref(ap), *ptrs, C.byref(res),
-                                    C.byref(st)), "rtw_render_adaptive")
+    if window:
+        check(lib().rtw_render_adaptive_window(ds.handle, C.byref(cam), C.byref(prm), C.byref(ap), window, *ptrs,
+                                               C.byref(res), C.byref(st)), "rtw_render_adaptive_window")
+    else:
+        check(lib().rtw_render_adaptive(ds.handle, C.byref(cam), C.byref(prm), C.byref(ap), *ptrs, C.byref(res),
+                                        C.byref(st)), "rtw_render_adaptive")
     c_host = counts if isinstance(counts, np.ndarray) else counts.cpu().numpy()
     history = [(b, c, int((c_host > b).sum())) for b, c in adaptive_schedule(min_spp, max_spp, batch)[:res.rounds]]
     out = {"accum": accum, "accum_sq": accum_sq, "counts": counts, "rounds": res.rounds, "samples": res.samples,
