@@ -233,6 +233,34 @@ ADAPTIVE_WINDOW_SIGNATURES = {
                                              C.c_void_p, C.POINTER(rtw_adaptive_result), C.POINTER(rtw_stats)]),
 }
 
+
+class rtw_query_ray(C.Structure):
+    """include/rtw_query.h"""
+    _fields_ = [("o", C.c_double * 3), ("d", C.c_double * 3), ("time", C.c_double), ("t_max", C.c_double)]
+
+
+class rtw_query_hit(C.Structure):
+    """include/rtw_query.h"""
+    _fields_ = [("t", C.c_double), ("p", C.c_double * 3), ("n", C.c_double * 3), ("prim", C.c_int32),
+                ("material", C.c_int32)]
+
+
+class rtw_query_params(C.Structure):
+    """include/rtw_query.h"""
+    _fields_ = [("on_device", C.c_int32), ("precision", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+# the functions of include/rtw_query.h (its own header, its own table)
+QUERY_SIGNATURES = {
+    "rtw_trace_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(rtw_query_params),
+                                    C.c_void_p, C.POINTER(rtw_stats)]),
+    "rtw_trace_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(rtw_query_params),
+                                     C.c_void_p, C.POINTER(rtw_stats)]),
+    "rtw_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera_desc), C.POINTER(rtw_render_params), C.c_void_p,
+                                  C.c_void_p, C.c_uint64]),
+    "rtw_scene_query_trace": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
+}
+
 _lib = None
 
 
@@ -254,7 +282,8 @@ def load_library(path) -> C.CDLL:
                            f"`python -m raytracingweekend_amd.build` (there is no CPU fallback)")
     L = C.CDLL(str(path))
     for name, (res, args) in [*SIGNATURES.items(), *NOISE_SIGNATURES.items(), *ADAPTIVE_SIGNATURES.items(),
-                              *DENOISE_SIGNATURES.items(), *ADAPTIVE_WINDOW_SIGNATURES.items()]:
+                              *DENOISE_SIGNATURES.items(), *ADAPTIVE_WINDOW_SIGNATURES.items(),
+                              *QUERY_SIGNATURES.items()]:
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

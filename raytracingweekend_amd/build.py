@@ -42,17 +42,20 @@ DEVICE = [f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 HOST_SOURCES = sorted((CSRC / "host").glob("*.cpp"))
 DEVICE_SOURCES = sorted(CSRC.glob("*.hip"))
 PUBLIC_HEADERS = [ROOT / "include" / "rtw_gpu.h", ROOT / "include" / "rtw_noise.h", ROOT / "include" / "rtw_adaptive.h",
-                  ROOT / "include" / "rtw_denoise.h", ROOT / "include" / "rtw_adaptive_window.h"]
+                  ROOT / "include" / "rtw_denoise.h", ROOT / "include" / "rtw_adaptive_window.h",
+                  ROOT / "include" / "rtw_query.h"]
 HEADERS = sorted(list(CSRC.rglob("*.h")) + PUBLIC_HEADERS)
 # what the device sources include: the build id and the kernels' rebuilds
 # follow these only (the host scene API headers under csrc/host/rtw/ do not
 # reach the kernels; host/scene_layout.h and host/render_plan.h do:
 # upload_scene, the handle and render_accumulate hold their result types by
 # value; host/moments.h, host/adaptive.h, host/adaptive_window.h and
-# host/denoise.h hold the per-pixel functions both sides evaluate)
+# host/denoise.h hold the per-pixel functions both sides evaluate; host/query.h
+# holds the launch plan of a ray query)
 DEVICE_HEADERS = sorted([*CSRC.glob("rtw_*.h"), CSRC / "host" / "rtw_host_util.h", CSRC / "host" / "scene_layout.h",
                          CSRC / "host" / "render_plan.h", CSRC / "host" / "moments.h", CSRC / "host" / "adaptive.h",
-                         CSRC / "host" / "adaptive_window.h", CSRC / "host" / "denoise.h", *PUBLIC_HEADERS])
+                         CSRC / "host" / "adaptive_window.h", CSRC / "host" / "denoise.h", CSRC / "host" / "query.h",
+                         *PUBLIC_HEADERS])
 # RCCL for rtw_render_multi (multi.cpp); the same librccl.so.1 torch loads
 LIBS = ["-L/opt/rocm/lib", "-lrccl"]
 

@@ -1246,9 +1246,24 @@ __device__ unsigned long long g_walk[32][64];  // clock per media-walk position 
 // primitive is deterministic; the second walk re-accepts only what the first
 // kept).  With media, the second walk can only change the result through the
 // media's fresh draws, so it re-evaluates just the media, in list order.
-template <int F, class STK>
-RTW_D hit_state world_closest(const scene& S, const ray& r, uint32_t& rng, STK& stk) {
-    hit_state h{in_place<kDblMaxBits>(), -1, false};
+//
+// Q selects what the walk is for.  kWalkRender: a render's walk, closest t
+// from DBL_MAX (materialised in place).  kWalkFrom (rtw_query.h): the same
+// walk started at the caller's t_start -- the reference's t_max; a rect at
+// exactly t_start is accepted and a sphere is not, by the comparisons every
+// test already makes against the closest t so far and better()'s rule for a
+// walk without a winner.  kWalkAny (media-free forms only): started at t_start
+// and left at the first accepted hit -- h.prim != -1 then says what the
+// closest walk's would, h.t and the winner are whichever hit came first.
+constexpr int kWalkRender = 0, kWalkFrom = 1, kWalkAny = 2;
+template <int F, int Q, class STK>
+RTW_D hit_state world_walk(const scene& S, const ray& r, uint32_t& rng, STK& stk, double t_start) {
+    static_assert(Q != kWalkAny || (F & F_MEDIA) == 0, "a medium's draws need the whole closest walk");
+    hit_state h{0.0, -1, false};
+    if constexpr (Q == kWalkRender)
+        h.t = in_place<kDblMaxBits>();
+    else
+        h.t = t_start;
     if constexpr ((F & F_WBVH) != 0 && (F & F_MEDIA) == 0) {
         const double fc = motion_frac(S, r.t, S.mv_common != 0);  // transforms keep the ray's time
         const slab_ray sr = make_slab_ray(S, r);
@@ -1314,6 +1329,10 @@ RTW_D hit_state world_closest(const scene& S, const ray& r, uint32_t& rng, STK& 
                 }
                 if (__builtin_amdgcn_ballot_w64(lc != 0) == 0) break;
                 if (lc != 0) leaf(la, lc);
+                // any-hit: a lane with a hit drops its stack and its node, so
+                // the ballots above count it as done
+                if constexpr (Q == kWalkAny)
+                    if (h.prim != -1) sp = 0, have = false;
             }
         } else {
             while (sp > 0) {
@@ -1322,6 +1341,8 @@ RTW_D hit_state world_closest(const scene& S, const ray& r, uint32_t& rng, STK& 
                 const int cnt = node_count(nd);
                 if (cnt > 0) {
                     leaf(nd.a, cnt);
+                    if constexpr (Q == kWalkAny)
+                        if (h.prim != -1) break;
                 } else if (sp + 2 <= STK::cap) {  // always true: depth checked at upload
                     push_children(nd, dneg, stk, sp);
                 }
@@ -1362,6 +1383,8 @@ RTW_D hit_state world_closest(const scene& S, const ray& r, uint32_t& rng, STK& 
             }
         } else {
             for (int ri = 0; ri < S.n_runs; ++ri) {
+                if constexpr (Q == kWalkAny)
+                    if (h.prim != -1) break;  // any-hit: the runs before this one gave a hit
                 // one scan site for plain runs and transformed groups alike
                 const int ei = ld(&S.runs[ri].entry);
                 if ((F & F_YSPH) && ei == WORLD_RUN_YSPHERES) {
@@ -1385,10 +1408,20 @@ RTW_D hit_state world_closest(const scene& S, const ray& r, uint32_t& rng, STK& 
         return h;
     }
 }
+template <int F, class STK>
+RTW_D hit_state world_closest(const scene& S, const ray& r, uint32_t& rng, STK& stk) {
+    return world_walk<F, kWalkRender>(S, r, rng, stk, 0.0);
+}
 template <int F>
 RTW_D hit_state world_closest(const scene& S, const ray& r, uint32_t& rng) {
     local_stack stk;
     return world_closest<F>(S, r, rng, stk);
+}
+// ... of a ray query (rtw_query.h): started at t_max; ANY: left at the first hit
+template <int F, bool ANY = false>
+RTW_D hit_state world_closest_from(const scene& S, const ray& r, uint32_t& rng, double t_max) {
+    local_stack stk;
+    return world_walk<F, ANY ? kWalkAny : kWalkFrom>(S, r, rng, stk, t_max);
 }
 
 // Reconstruct the hit record (p, normal, material) of a winner exactly as

@@ -45,6 +45,7 @@
 #include "host/adaptive.h"
 #include "host/adaptive_window.h"
 #include "host/denoise.h"
+#include "host/query.h"
 #include "host/render_plan.h"
 #include "host/rtw_host_util.h"
 #include "host/scene_layout.h"
@@ -2231,6 +2232,97 @@ __global__ __launch_bounds__(kBlock) void k_features(scene S, job_t J, double* _
         o[0] = double2{alb.x, alb.y}, o[1] = double2{alb.z, nrm.x}, o[2] = double2{nrm.y, nrm.z}, o[3] = double2{invt, cov};
     }
 }
+
+// ---- rtw_query.h: the caller's rays -------------------------------------------
+// A thread owns whole rays (grid stride over the launch's rays; at most
+// kQueryLaunchMax of them, so the 32-bit index cannot wrap).  A record is 64
+// bytes: four 16-byte loads / stores per lane, as k_features moves a pixel's
+// sums -- a wave's four instructions together read 4 KiB of consecutive bytes,
+// every line whole, and one world walk per 128 bytes moved leaves nothing for
+// an LDS transpose to win.
+struct query_args {
+    const rtw_query_ray* rays;
+    uint32_t* rng;     // null: the scene has no media, no state is read or written
+    uint32_t n;
+    uint32_t check;    // the scene has a BVH and moving spheres: ray times must lie in [sh0, sh1]
+    double sh0, sh1;   // the shutter the BVH's boxes cover
+    uint32_t* bad;     // counter of rays outside it (check != 0)
+};
+struct query_ray_in {
+    ray r;
+    double t_max;
+    bool walk;  // t_max > 0.001f and the ray's time can be traced
+};
+__device__ __forceinline__ query_ray_in load_query_ray(const query_args& Q, uint32_t k) {
+    const double2* in = reinterpret_cast<const double2*>(Q.rays + k);
+    const double2 a = in[0], b = in[1], c = in[2], d = in[3];
+    query_ray_in x;
+    x.r.o = d3{a.x, a.y, b.x}, x.r.d = d3{b.y, c.x, c.y}, x.r.t = d.x;
+    x.t_max = d.y;
+    x.walk = x.t_max > kTMin;  // (false for NaN)
+    if (Q.check && !(x.r.t >= Q.sh0 && x.r.t <= Q.sh1)) {
+        atomicAdd(Q.bad, 1u);
+        x.walk = false;
+    }
+    return x;
+}
+
+template <int F>
+__global__ __launch_bounds__(kBlock) void k_query(scene S, query_args Q, rtw_query_hit* __restrict__ hits) {
+    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < Q.n; k += gridDim.x * kBlock) {
+        const query_ray_in x = load_query_ray(Q, k);
+        hit_state h{x.t_max, -1, false};
+        if (x.walk) {
+            uint32_t rng = 0;
+            if constexpr ((F & F_MEDIA) != 0) rng = Q.rng[k];
+            h = world_closest_from<F>(S, x.r, rng, x.t_max);
+            if constexpr ((F & F_MEDIA) != 0) Q.rng[k] = rng;
+        }
+        d3 p{0, 0, 0}, n{0, 0, 0};
+        int mat = -1;
+        if (h.prim != -1) {
+            bool rect;
+            d3 sl;
+            hit_record<true, false, false>(S, x.r, h, p, n, mat, rect, sl);
+        }
+        double2* o = reinterpret_cast<double2*>(hits + k);
+        const long long ids = (long long)(((unsigned long long)(uint32_t)mat << 32) | (uint32_t)h.prim);
+        o[0] = double2{h.t, p.x}, o[1] = double2{p.y, p.z}, o[2] = double2{n.x, n.y};
+        o[3] = double2{n.z, __longlong_as_double(ids)};
+    }
+}
+
+// occluded[k] = k_query's prim != -1.  Media-free forms leave the walk at the
+// first accepted hit (world_walk kWalkAny); with media the closest walk runs
+// unchanged, draws and states as k_query's.
+template <int F>
+__global__ __launch_bounds__(kBlock) void k_occluded(scene S, query_args Q, uint8_t* __restrict__ occluded) {
+    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < Q.n; k += gridDim.x * kBlock) {
+        const query_ray_in x = load_query_ray(Q, k);
+        hit_state h{x.t_max, -1, false};
+        if (x.walk) {
+            uint32_t rng = 0;
+            if constexpr ((F & F_MEDIA) != 0) rng = Q.rng[k];
+            h = world_closest_from<F, (F & F_MEDIA) == 0>(S, x.r, rng, x.t_max);
+            if constexpr ((F & F_MEDIA) != 0) Q.rng[k] = rng;
+        }
+        occluded[k] = h.prim != -1 ? 1 : 0;
+    }
+}
+
+// rtw_camera_rays: camera_sample of the pass-local sample ids [q0, q0 + count)
+// with the ray and the stream's state after the camera's draws stored.
+__global__ __launch_bounds__(kBlock) void k_camera_rays(job_t J, uint32_t q0, uint32_t count,
+                                                        rtw_query_ray* __restrict__ rays, uint32_t* __restrict__ rng_out) {
+    for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < count; k += (uint64_t)gridDim.x * kBlock) {
+        uint32_t rng;
+        const ray r = camera_sample<true, false>(J, q0 + (uint32_t)k, rng);
+        double2* o = reinterpret_cast<double2*>(rays + k);
+        o[0] = double2{r.o.x, r.o.y}, o[1] = double2{r.o.z, r.d.x}, o[2] = double2{r.d.y, r.d.z};
+        o[3] = double2{r.t, __builtin_inf()};
+        if (rng_out) rng_out[k] = rng;
+    }
+}
 #endif
 
 // ======================================================================
@@ -2294,6 +2386,9 @@ struct handle_t {
     dev_buf features;     // the device copy of a host feature buffer
     dev_buf dn_state[2];  // rtw_denoise_device: the iteration state, ping-pong (rtw_dn_state)
     dev_buf dn_geo, dn_alb;  // ... and the per-pixel features the passes only read
+    // rtw_query.h
+    dev_buf q_rays, q_out, q_rng;  // one staged chunk of a host-buffer query (query_plan)
+    dev_buf q_bad;                 // counter of rays whose time the BVH's boxes do not cover
     dev_buf ctrs;
     dev_buf camera;                // device copy of the call's camera
     rtw_camera_desc cam_host{};    // its source (lives until the copy ran)
@@ -3843,4 +3938,199 @@ extern "C" int rtw_finalize_canvas_mean_device(void* handle, const double* mean,
     HIPCHK(hipSetDevice(h->device));
     if (int rc = check_handle_ptrs(h, what, {mean, canvas})) return rc;
     return launch_finalize(h, mean, nx, ny, rtw_div_none{}, canvas);
+}
+
+// ======================================================================
+// rtw_query.h
+// ======================================================================
+#if !RTW_STRICT_RADIANCE
+namespace {
+// k_query<f> and k_occluded<f> of every entry of kIntersectList (its traversal feature sets)
+template <size_t... I>
+std::array<const void*, sizeof...(I)> query_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_query<kIntersectList[I].f>)...};
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> occluded_rows(std::index_sequence<I...>) {
+    return {reinterpret_cast<const void*>(&k_occluded<kIntersectList[I].f>)...};
+}
+const auto kQueryRows = query_rows(std::make_index_sequence<kIntersectList.size()>{});
+const auto kOccludedRows = occluded_rows(std::make_index_sequence<kIntersectList.size()>{});
+
+// The trace of a checked, non-empty call.  flags: rtw_trace_occluded.
+int query_trace(handle_t* h, const char* what, const rtw_query_ray* rays, uint64_t n, uint32_t* rng,
+                const rtw_query_params* prm, void* out, bool flags, rtw_stats* stats) {
+    const inst in = features_inst(h);
+    const int at = index_of(kIntersectList, in);
+    if (at < 0) return rtw_fail(RTW_ERR_HIP, "no such instantiation: k_query");
+    const bool media = (in.f & F_MEDIA) != 0;
+    if (!media) rng = nullptr;  // never touched
+    const size_t stride = flags ? 1 : sizeof(rtw_query_hit);
+    HIPCHK(hipSetDevice(h->device));
+    if (prm->on_device)
+        if (int rc = check_handle_ptrs(h, what, {rays, rng, out})) return rc;
+    const query_plan P = rtw_query_plan(n, !prm->on_device, stride, media);
+    if (int rc = h->q_rays.ensure(P.bytes_rays)) return rc;
+    if (int rc = h->q_out.ensure(P.bytes_out)) return rc;
+    if (int rc = h->q_rng.ensure(P.bytes_rng)) return rc;
+    hipStream_t st = h->stream;
+    uint32_t* bad = nullptr;
+    if (h->facts.bvh_motion) {
+        if (int rc = h->q_bad.ensure(16)) return rc;
+        bad = static_cast<uint32_t*>(h->q_bad.p);
+        HIPCHK(hipMemsetAsync(bad, 0, 4, st));
+    }
+    hipEvent_t ev_begin = event_at(h, 0), ev_end = event_at(h, 1);
+    if (!ev_begin || !ev_end) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
+    HIPCHK(hipEventRecord(ev_begin, st));
+    const void* fn = flags ? kOccludedRows[at] : kQueryRows[at];
+    for (uint64_t c = 0; c < P.n_chunks; ++c) {
+        const query_span ch = rtw_query_chunk(P, c);
+        // the chunk's buffers on the device: the caller's, or the staged copies
+        const rtw_query_ray* r_dev = rays + ch.first;
+        uint32_t* g_dev = rng ? rng + ch.first : nullptr;
+        char* o_dev = static_cast<char*>(out) + ch.first * stride;
+        if (P.staged) {
+            r_dev = static_cast<const rtw_query_ray*>(h->q_rays.p);
+            o_dev = static_cast<char*>(h->q_out.p);
+            HIPCHK(hipMemcpyAsync(h->q_rays.p, rays + ch.first, ch.count * sizeof(rtw_query_ray), hipMemcpyHostToDevice, st));
+            if (rng) {
+                g_dev = static_cast<uint32_t*>(h->q_rng.p);
+                HIPCHK(hipMemcpyAsync(g_dev, rng + ch.first, ch.count * 4, hipMemcpyHostToDevice, st));
+            }
+        }
+        for (uint64_t l = 0, nl = rtw_query_launches(P, ch); l < nl; ++l) {
+            const query_span ls = rtw_query_launch(P, ch, l);
+            const uint64_t rel = ls.first - ch.first;
+            query_args Q{};
+            Q.rays = r_dev + rel;
+            Q.rng = g_dev ? g_dev + rel : nullptr;
+            Q.n = (uint32_t)ls.count;
+            Q.check = bad ? 1u : 0u;
+            Q.sh0 = h->facts.shutter0, Q.sh1 = h->facts.shutter1;
+            Q.bad = bad;
+            const int grid = (int)std::min<uint64_t>((ls.count + kBlock - 1) / kBlock, (uint64_t)h->grid);
+            if (flags)
+                launch(fn, grid, kBlock, 0, st, h->S, Q, reinterpret_cast<uint8_t*>(o_dev + rel * stride));
+            else
+                launch(fn, grid, kBlock, 0, st, h->S, Q, reinterpret_cast<rtw_query_hit*>(o_dev + rel * stride));
+            HIPCHK(hipGetLastError());
+            stats->launches_intersect++;
+        }
+        if (P.staged) {
+            HIPCHK(hipMemcpyAsync(static_cast<char*>(out) + ch.first * stride, o_dev, ch.count * stride, hipMemcpyDeviceToHost, st));
+            if (rng) HIPCHK(hipMemcpyAsync(rng + ch.first, g_dev, ch.count * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIPCHK(hipEventRecord(ev_end, st));
+    uint32_t n_bad = 0;
+    if (bad) HIPCHK(hipMemcpyAsync(&n_bad, bad, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end));
+    stats->ms_total = ms;
+    stats->samples = stats->segments = n;
+    stats->bytes_intersect = 68.0 * (double)n;
+    if (n_bad)
+        return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": " + std::to_string(n_bad) +
+                                             " rays have a time outside the shutter the scene's BVH was built for "
+                                             "(moving spheres)");
+    return RTW_OK;
+}
+}  // namespace
+#endif
+
+static int query_entry(const char* what, void* handle, const rtw_query_ray* rays, uint64_t n, uint32_t* rng,
+                       const rtw_query_params* prm, void* out, bool flags, rtw_stats* out_stats) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    // (the strict build refuses before it reads the handle)
+    const bool media = !RTW_STRICT_RADIANCE && h && (h->facts.features & F_MEDIA) != 0;
+    if (int rc = rtw_query_check_args(what, h, rays, n, rng, prm, out, flags ? 1 : sizeof(rtw_query_hit), media,
+                                      RTW_STRICT_RADIANCE != 0))
+        return rc;
+    rtw_stats stats;
+    std::memset(&stats, 0, sizeof stats);
+    int rc = RTW_OK;
+#if !RTW_STRICT_RADIANCE
+    if (n) rc = query_trace(h, what, rays, n, rng, prm, out, flags, &stats);
+#endif
+    if (!rc && out_stats) *out_stats = stats;
+    return rc;
+}
+
+extern "C" int rtw_trace_closest(void* handle, const rtw_query_ray* rays, uint64_t n, uint32_t* rng,
+                                 const rtw_query_params* prm, rtw_query_hit* hits, rtw_stats* out_stats) {
+    return query_entry("rtw_trace_closest", handle, rays, n, rng, prm, hits, false, out_stats);
+}
+
+extern "C" int rtw_trace_occluded(void* handle, const rtw_query_ray* rays, uint64_t n, uint32_t* rng,
+                                  const rtw_query_params* prm, uint8_t* occluded, rtw_stats* out_stats) {
+    return query_entry("rtw_trace_occluded", handle, rays, n, rng, prm, occluded, true, out_stats);
+}
+
+extern "C" int rtw_scene_query_trace(void* handle, char closest[128], char occluded[128]) {
+    const handle_t* h = static_cast<const handle_t*>(handle);
+    if (!h || !closest || !occluded) return rtw_fail(RTW_ERR_INVALID, "rtw_scene_query_trace: null argument");
+    if (RTW_STRICT_RADIANCE)
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build has no query kernels (rtw_trace_closest)");
+    const int f = features_inst(h).f;
+    std::snprintf(closest, 128, "%s", kname("k_query", f, -1).c_str());
+    std::snprintf(occluded, 128, "%s", kname("k_occluded", f, -1).c_str());
+    return RTW_OK;
+}
+
+extern "C" int rtw_camera_rays(void* handle, const rtw_camera_desc* camera, const rtw_render_params* prm,
+                               rtw_query_ray* rays, uint32_t* rng_out, uint64_t capacity) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    if (!h || !camera || !prm) return rtw_fail(RTW_ERR_INVALID, "rtw_camera_rays: null argument");
+#if RTW_STRICT_RADIANCE
+    return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build has no query kernels (rtw_camera_rays)");
+#else
+    // the render's plan of the same call (as rtw_render_features): its
+    // refusals, sample and row ranges, camera and job fields; one pass holds
+    // the whole call, so q is the index the header states
+    rtw_render_params R = *prm;
+    R.precision = RTW_PRECISION_FP64, R.max_depth = 1;
+    call_plan P;
+    if (int rc = rtw_plan_call(R, *camera, h->facts, rays, nullptr, pass_budget_samples(), 0, &P)) return rc;
+    const uint64_t total = (uint64_t)P.spp_count * P.npix;
+    if (int rc = rtw_query_check_camera_args(rays, rng_out, capacity, total, R.accum_on_device != 0)) return rc;
+    if (total == 0) return RTW_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (R.accum_on_device)
+        if (int rc = check_handle_ptrs(h, "rtw_camera_rays", {rays, rng_out})) return rc;
+    P.pass_spp = (uint64_t)P.spp_count;
+    hipStream_t st = h->stream;
+    if (int rc = h->camera.ensure(P.bytes.camera)) return rc;
+    h->cam_host = P.cam_dev;
+    HIPCHK(hipMemcpyAsync(h->camera.p, &h->cam_host, sizeof(rtw_camera_desc), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_recips, dim3(1), dim3(64), 0, st,
+                       reinterpret_cast<double*>(static_cast<char*>(h->camera.p) + sizeof(rtw_camera_desc)), R.nx, R.ny);
+    HIPCHK(hipGetLastError());
+    job_t J = make_job(h, P, R);
+    J.L = nullptr;
+    set_pass(J, rtw_plan_pass(P, R, 0));
+    const query_plan Q = rtw_query_plan(total, !R.accum_on_device, 0, rng_out != nullptr);
+    if (int rc = h->q_rays.ensure(Q.bytes_rays)) return rc;
+    if (int rc = h->q_rng.ensure(Q.bytes_rng)) return rc;
+    for (uint64_t c = 0; c < Q.n_chunks; ++c) {
+        const query_span ch = rtw_query_chunk(Q, c);
+        rtw_query_ray* r_dev = Q.staged ? static_cast<rtw_query_ray*>(h->q_rays.p) : rays + ch.first;
+        uint32_t* g_dev = !rng_out ? nullptr : Q.staged ? static_cast<uint32_t*>(h->q_rng.p) : rng_out + ch.first;
+        for (uint64_t l = 0, nl = rtw_query_launches(Q, ch); l < nl; ++l) {
+            const query_span ls = rtw_query_launch(Q, ch, l);
+            const uint64_t rel = ls.first - ch.first;
+            const int grid = (int)std::min<uint64_t>((ls.count + kBlock - 1) / kBlock, (uint64_t)h->grid);
+            hipLaunchKernelGGL(k_camera_rays, dim3(grid), dim3(kBlock), 0, st, J, (uint32_t)ls.first, (uint32_t)ls.count,
+                               r_dev + rel, g_dev ? g_dev + rel : nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        if (Q.staged) {
+            HIPCHK(hipMemcpyAsync(rays + ch.first, r_dev, ch.count * sizeof(rtw_query_ray), hipMemcpyDeviceToHost, st));
+            if (rng_out) HIPCHK(hipMemcpyAsync(rng_out + ch.first, g_dev, ch.count * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return RTW_OK;
+#endif
 }

@@ -10,6 +10,14 @@
 //              [--adaptive X [--min-spp 16] [--noise-batch B] [--noise-floor 0.01]
 //                            [--adaptive-window R]]
 //              [--denoise [--denoise-iterations 5]]
+//   rtw_render --scene S [--bvh] --rays rays.bin --hits hits.bin [--occluded] [--rng rng.bin]
+//
+// --rays rays.bin --hits hits.bin traces the caller's rays instead of rendering
+// (rtw_query.h): rays.bin holds raw rtw_query_ray records, hits.bin receives
+// raw rtw_query_hit records (rtw_trace_closest) or, with --occluded, one byte
+// per ray (rtw_trace_occluded).  A scene with media needs --rng rng.bin, one
+// uint32 minstd state per ray; the states after the trace are written back to
+// that file.  Prints one "Query:" line: kernel, rays, milliseconds.  One GPU.
 //
 // --noise renders through rtw_render_accumulate_moments (rtw_noise.h) and
 // prints the image-wide noise estimate of the --spp samples.  --noise-target X
@@ -56,6 +64,75 @@
 #include "rtw_adaptive_window.h"
 #include "rtw_denoise.h"
 #include "rtw_noise.h"
+#include "rtw_query.h"
+
+namespace {
+// --rays: trace the file's rays on `handle`, write the hits (or flags)
+int run_query(void* handle, const std::string& rays_path, const std::string& hits_path, const std::string& rng_path,
+              bool occluded) {
+    auto slurp = [](const std::string& path, std::vector<char>& out) {
+        FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) return false;
+        std::fseek(f, 0, SEEK_END);
+        const long n = std::ftell(f);
+        std::fseek(f, 0, SEEK_SET);
+        out.resize(n > 0 ? (size_t)n : 0);
+        const bool ok = out.empty() || std::fread(out.data(), 1, out.size(), f) == out.size();
+        std::fclose(f);
+        return ok;
+    };
+    auto spill = [](const std::string& path, const void* data, size_t bytes) {
+        FILE* f = std::fopen(path.c_str(), "wb");
+        if (!f) return false;
+        const bool ok = bytes == 0 || std::fwrite(data, 1, bytes, f) == bytes;
+        return std::fclose(f) == 0 && ok;
+    };
+    std::vector<char> raw, raw_rng;
+    if (!slurp(rays_path, raw) || raw.size() % sizeof(rtw_query_ray)) {
+        std::fprintf(stderr, "--rays %s: not a file of %zu-byte ray records\n", rays_path.c_str(), sizeof(rtw_query_ray));
+        return 1;
+    }
+    const uint64_t n = raw.size() / sizeof(rtw_query_ray);
+    std::vector<rtw_query_ray> rays(n);
+    if (n) std::memcpy(rays.data(), raw.data(), raw.size());
+    std::vector<uint32_t> rng;
+    if (!rng_path.empty()) {
+        if (!slurp(rng_path, raw_rng) || raw_rng.size() != n * 4) {
+            std::fprintf(stderr, "--rng %s: expected one uint32 state per ray\n", rng_path.c_str());
+            return 1;
+        }
+        rng.resize(n);
+        if (n) std::memcpy(rng.data(), raw_rng.data(), raw_rng.size());
+    }
+    rtw_query_params qp;
+    std::memset(&qp, 0, sizeof qp);
+    qp.precision = RTW_PRECISION_FP64;
+    rtw_stats st;
+    std::memset(&st, 0, sizeof st);
+    char k_closest[128] = "", k_occluded[128] = "";
+    if (rtw_scene_query_trace(handle, k_closest, k_occluded) != RTW_OK) {
+        std::fprintf(stderr, "query: %s\n", rtw_last_error());
+        return 1;
+    }
+    std::vector<rtw_query_hit> hits(occluded ? 0 : n);
+    std::vector<uint8_t> flags(occluded ? n : 0);
+    uint32_t* g = rng.empty() ? nullptr : rng.data();
+    const int rc = occluded ? rtw_trace_occluded(handle, rays.data(), n, g, &qp, flags.data(), &st)
+                            : rtw_trace_closest(handle, rays.data(), n, g, &qp, hits.data(), &st);
+    if (rc != RTW_OK) {
+        std::fprintf(stderr, "query: %s\n", rtw_last_error());
+        return 1;
+    }
+    const bool wrote = occluded ? spill(hits_path, flags.data(), flags.size())
+                                : spill(hits_path, hits.data(), hits.size() * sizeof(rtw_query_hit));
+    if (!wrote || (g && !spill(rng_path, rng.data(), rng.size() * 4))) {
+        std::fprintf(stderr, "cannot write %s\n", hits_path.c_str());
+        return 1;
+    }
+    std::printf("Query: %s  rays %llu  %.3f ms\n", occluded ? k_occluded : k_closest, (unsigned long long)n, st.ms_total);
+    return 0;
+}
+}  // namespace
 
 int main(int argc, char** argv) {
     std::string scene_name = "cornell_box", out = "1.ppm", image;
@@ -70,6 +147,8 @@ int main(int argc, char** argv) {
     bool window_given = false;
     bool denoise = false;
     int denoise_iterations = -1;  // (not given: the library's default)
+    std::string rays_path, hits_path, rng_path;
+    bool occluded = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -98,6 +177,10 @@ int main(int argc, char** argv) {
         else if (a == "--min-spp") min_spp = std::atoi(next());
         else if (a == "--noise-floor") noise_floor = std::atof(next());
         else if (a == "--denoise") denoise = true;
+        else if (a == "--rays") rays_path = next();
+        else if (a == "--hits") hits_path = next();
+        else if (a == "--rng") rng_path = next();
+        else if (a == "--occluded") occluded = true;
         else if (a == "--denoise-iterations") denoise_iterations = std::atoi(next()), denoise = true;
         else if (a == "--precision") {
             const std::string v = next();
@@ -144,6 +227,13 @@ int main(int argc, char** argv) {
         return 2;
     }
 
+    if (rays_path.empty() != hits_path.empty() || (rays_path.empty() && (occluded || !rng_path.empty())) ||
+        (!rays_path.empty() && (gpus != 1 || noise || adaptive || denoise))) {
+        std::fprintf(stderr, "--rays FILE --hits FILE [--occluded] [--rng FILE] go together, on one GPU, without a render's "
+                             "options\n");
+        return 2;
+    }
+
     std::unique_ptr<scene> sc;
     if (!image.empty()) {
         if (scene_name != "textured") {
@@ -179,6 +269,12 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "upload: %s\n", rtw_last_error());
             return 1;
         }
+    if (!rays_path.empty()) {
+        const int rc = run_query(h[0], rays_path, hits_path, rng_path, occluded);
+        rtw_scene_free(h[0]);
+        rtw_scene_desc_free(desc);
+        return rc;
+    }
     const rtw_camera_desc cam = sc->GetCamera().desc();
     rtw_render_params p;
     std::memset(&p, 0, sizeof p);

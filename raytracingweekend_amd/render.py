@@ -20,6 +20,11 @@ from . import _abi
 from ._abi import check, lib
 
 
+# rtw_query_hit (include/rtw_query.h) as a numpy record: 64 bytes
+QUERY_HIT_DTYPE = np.dtype([("t", np.float64), ("p", np.float64, 3), ("n", np.float64, 3), ("prim", np.int32),
+                            ("material", np.int32)])
+
+
 class SceneDesc:
     """A reference scene built with the host C++ scene API and flattened
     (rtw_scene_builtin).  Owns the library-allocated rtw_scene_desc."""
@@ -376,6 +381,102 @@ class DeviceScene:
         """canvas = min(sqrt(mean), 1) of a denoised mean
         (rtw_finalize_canvas_mean[_device])."""
         return self._finalize(mean, nx, ny, "mean")
+
+    # ---- ray queries (include/rtw_query.h) ------------------------------------
+    def _rng_ptr(self, rng, n: int, want_device: bool):
+        """Pointer of n minstd states: a uint32 numpy array, or a torch int32 /
+        uint32 tensor on this device (the same kind as the rays)."""
+        if rng is None:
+            return None
+        if isinstance(rng, np.ndarray):
+            if want_device or rng.dtype != np.uint32 or rng.size != n or not rng.flags["C_CONTIGUOUS"]:
+                raise ValueError("rng must be a contiguous uint32 array of n states, of the rays' kind")
+            return rng.ctypes.data_as(C.c_void_p)
+        import torch
+        kinds = [torch.int32] + ([torch.uint32] if hasattr(torch, "uint32") else [])
+        if (not want_device or rng.dtype not in kinds or rng.numel() != n or not rng.is_contiguous() or not rng.is_cuda
+                or rng.device.index != self.device):
+            raise ValueError("rng must be a contiguous int32 / uint32 tensor of n states on this scene's GPU")
+        return C.c_void_p(rng.data_ptr())
+
+    def trace_rays(self, rays, rng=None, *, occluded: bool = False):
+        """rtw_trace_closest / rtw_trace_occluded of the caller's rays: an
+        (n, 8) float64 numpy array or CUDA tensor of this device with rows
+        (o, d, time, t_max).  `rng` (n minstd states, updated in place) is
+        needed for a scene with media only.  Results come back in the rays'
+        kind.  Closest: a structured array with fields t, p, n, prim, material
+        (rtw_query_hit), or for tensors a dict of views t, p, n, prim,
+        material over one (n, 8) float64 buffer, also under "records".
+        occluded=True: n uint8 flags.  Tensors are passed by data_ptr(),
+        nothing is copied through the host.  The call's stats are left in
+        self.last_query_stats."""
+        on_device = not isinstance(rays, np.ndarray)
+        if on_device:
+            import torch
+            if (rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous()
+                    or not rays.is_cuda or rays.device.index != self.device):
+                raise ValueError("rays must be a contiguous (n, 8) float64 tensor on this scene's GPU")
+            n = rays.shape[0]
+            out = (torch.empty(n, dtype=torch.uint8, device=rays.device) if occluded
+                   else torch.empty((n, 8), dtype=torch.float64, device=rays.device))
+            torch.cuda.synchronize(rays.device)
+            p_rays, p_out = C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr())
+        else:
+            if rays.dtype != np.float64 or rays.ndim != 2 or rays.shape[1] != 8 or not rays.flags["C_CONTIGUOUS"]:
+                raise ValueError("rays must be a contiguous (n, 8) float64 array")
+            n = rays.shape[0]
+            out = np.empty(n, dtype=np.uint8) if occluded else np.empty(n, dtype=QUERY_HIT_DTYPE)
+            p_rays, p_out = rays.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+        prm = _abi.rtw_query_params(on_device=int(on_device), precision=_abi.RTW_PRECISION_FP64)
+        st = _abi.rtw_stats()
+        fn = lib().rtw_trace_occluded if occluded else lib().rtw_trace_closest
+        check(fn(self.handle, p_rays, n, self._rng_ptr(rng, n, on_device), C.byref(prm), p_out, C.byref(st)),
+              "rtw_trace_occluded" if occluded else "rtw_trace_closest")
+        self.last_query_stats = st.as_dict()
+        if occluded or not on_device:
+            return out
+        import torch
+        ids = out[:, 7:8].view(torch.int32)
+        return {"records": out, "t": out[:, 0], "p": out[:, 1:4], "n": out[:, 4:7], "prim": ids[:, 0],
+                "material": ids[:, 1]}
+
+    def camera_rays(self, nx: int, ny: int, spp: int, seed: int = 0, *, spp_begin: int = 0, spp_count: int = 0,
+                    row_begin: int = 0, row_step: int = 1, device: bool = False,
+                    camera: Optional[_abi.rtw_camera_desc] = None):
+        """rtw_camera_rays: the first rays render_accumulate traces with the
+        same arguments, as (rays (n, 8) float64, rng n states after the
+        camera's draws), at the render's pass-local sample ids q = (s -
+        spp_begin) * npix + row * nx + i.  device=True: CUDA tensors (rng
+        int32) of this device, else numpy arrays (rng uint32)."""
+        step = row_step if row_step > 0 else 1
+        rows = max(0, (ny - row_begin + step - 1) // step)
+        count = spp_count if spp_count else spp - spp_begin
+        n = max(0, count) * rows * nx
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            rays = torch.empty((n, 8), dtype=torch.float64, device=dev)
+            rng = torch.empty(n, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+            p_rays, p_rng = C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr())
+        else:
+            rays, rng = np.empty((n, 8), dtype=np.float64), np.empty(n, dtype=np.uint32)
+            p_rays, p_rng = rays.ctypes.data_as(C.c_void_p), rng.ctypes.data_as(C.c_void_p)
+        prm = _abi.rtw_render_params(nx=nx, ny=ny, spp=spp, max_depth=1, seed=seed, spp_begin=spp_begin,
+                                     spp_count=spp_count, row_begin=row_begin, row_step=row_step,
+                                     accum_on_device=int(device), precision=_abi.PRECISIONS["fp64"])
+        cam = camera if camera is not None else self.scene.camera
+        if n == 0:
+            return rays, rng
+        check(lib().rtw_camera_rays(self.handle, C.byref(cam), C.byref(prm), p_rays, p_rng, n), "rtw_camera_rays")
+        return rays, rng
+
+    def query_trace(self) -> Tuple[str, str]:
+        """rtw_scene_query_trace: the kernels trace_rays launches, (closest,
+        occluded)."""
+        a, b = C.create_string_buffer(128), C.create_string_buffer(128)
+        check(lib().rtw_scene_query_trace(self.handle, a, b), "rtw_scene_query_trace")
+        return a.value.decode(), b.value.decode()
 
     def finalize_device(self, accum, nx: int, ny: int, spp: int, canvas=None):
         """canvas = min(sqrt(accum / spp), 1) on the GPU (torch float64 CUDA
