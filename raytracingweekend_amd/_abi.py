@@ -261,6 +261,22 @@ QUERY_SIGNATURES = {
     "rtw_scene_query_trace": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
 }
 
+
+
+class rtw_radiance_params(C.Structure):
+    """include/rtw_radiance.h"""
+    _fields_ = [("max_depth", C.c_int32), ("spp_begin", C.c_int32), ("spp_count", C.c_int32), ("on_device", C.c_int32),
+                ("seed", C.c_uint64), ("first_key", C.c_uint32), ("precision", C.c_int32),
+                ("wavefront_paths", C.c_int32), ("pad", C.c_int32)]
+
+
+# the functions of include/rtw_radiance.h (its own header, its own table)
+RADIANCE_SIGNATURES = {
+    "rtw_trace_radiance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(rtw_radiance_params),
+                                     C.c_void_p, C.POINTER(rtw_stats)]),
+    "rtw_scene_query_radiance": (C.c_int, [C.c_void_p, C.c_char_p]),
+}
+
 _lib = None
 
 
@@ -283,7 +299,7 @@ def load_library(path) -> C.CDLL:
     L = C.CDLL(str(path))
     for name, (res, args) in [*SIGNATURES.items(), *NOISE_SIGNATURES.items(), *ADAPTIVE_SIGNATURES.items(),
                               *DENOISE_SIGNATURES.items(), *ADAPTIVE_WINDOW_SIGNATURES.items(),
-                              *QUERY_SIGNATURES.items()]:
+                              *QUERY_SIGNATURES.items(), *RADIANCE_SIGNATURES.items()]:
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

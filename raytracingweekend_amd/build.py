@@ -43,7 +43,7 @@ HOST_SOURCES = sorted((CSRC / "host").glob("*.cpp"))
 DEVICE_SOURCES = sorted(CSRC.glob("*.hip"))
 PUBLIC_HEADERS = [ROOT / "include" / "rtw_gpu.h", ROOT / "include" / "rtw_noise.h", ROOT / "include" / "rtw_adaptive.h",
                   ROOT / "include" / "rtw_denoise.h", ROOT / "include" / "rtw_adaptive_window.h",
-                  ROOT / "include" / "rtw_query.h"]
+                  ROOT / "include" / "rtw_query.h", ROOT / "include" / "rtw_radiance.h"]
 HEADERS = sorted(list(CSRC.rglob("*.h")) + PUBLIC_HEADERS)
 # what the device sources include: the build id and the kernels' rebuilds
 # follow these only (the host scene API headers under csrc/host/rtw/ do not
@@ -51,10 +51,11 @@ HEADERS = sorted(list(CSRC.rglob("*.h")) + PUBLIC_HEADERS)
 # upload_scene, the handle and render_accumulate hold their result types by
 # value; host/moments.h, host/adaptive.h, host/adaptive_window.h and
 # host/denoise.h hold the per-pixel functions both sides evaluate; host/query.h
-# holds the launch plan of a ray query)
+# holds the launch plan of a ray query, host/radiance.h a radiance query's)
 DEVICE_HEADERS = sorted([*CSRC.glob("rtw_*.h"), CSRC / "host" / "rtw_host_util.h", CSRC / "host" / "scene_layout.h",
                          CSRC / "host" / "render_plan.h", CSRC / "host" / "moments.h", CSRC / "host" / "adaptive.h",
                          CSRC / "host" / "adaptive_window.h", CSRC / "host" / "denoise.h", CSRC / "host" / "query.h",
+                         CSRC / "host" / "radiance.h",
                          *PUBLIC_HEADERS])
 # RCCL for rtw_render_multi (multi.cpp); the same librccl.so.1 torch loads
 LIBS = ["-L/opt/rocm/lib", "-lrccl"]

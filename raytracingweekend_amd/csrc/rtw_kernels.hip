@@ -46,6 +46,7 @@
 #include "host/adaptive_window.h"
 #include "host/denoise.h"
 #include "host/query.h"
+#include "host/radiance.h"
 #include "host/render_plan.h"
 #include "host/rtw_host_util.h"
 #include "host/scene_layout.h"
@@ -206,10 +207,69 @@ __device__ __forceinline__ rtwf::fray camera_sample_f32(const job_t& J, const rt
     return rtwf::camera_ray(cam, u, v, rng);
 }
 
-template <bool ACTIVE = false>
+// A ray-sourced job (rtw_radiance.h): a fresh path starts from a record of the
+// caller's, not from the camera, so the job's camera fields are not read.  As
+// with the active list, job_t does not grow: the ray records lie over `cam`
+// (a pointer already), the caller's stream states (null: keyed streams) over
+// row_begin / row_step, and the first ray's RNG key over nx.  Only
+// k_regen_rays and the F_RAYS rows read them (ray_sample).
+static_assert(offsetof(job_t, cam) == 0 && sizeof(job_t::cam) == sizeof(const rtw_query_ray*) &&
+                  offsetof(job_t, cam) + sizeof(job_t::cam) <= offsetof(job_t, seed_mix),
+              "the ray records' pointer overlays cam and nothing else");
+static_assert(offsetof(job_t, row_begin) % 8 == 0 && offsetof(job_t, row_step) == offsetof(job_t, row_begin) + 4 &&
+                  sizeof(job_t::row_begin) + sizeof(job_t::row_step) == sizeof(const uint32_t*),
+              "the caller's stream states' pointer overlays row_begin / row_step, as the active list's does");
+static_assert(sizeof(job_t::nx) == sizeof(uint32_t) &&
+                  (offsetof(job_t, nx) + sizeof(job_t::nx) <= offsetof(job_t, row_begin) ||
+                   offsetof(job_t, nx) >= offsetof(job_t, row_step) + sizeof(job_t::row_step)) &&
+                  offsetof(job_t, nx) >= offsetof(job_t, cam) + sizeof(job_t::cam),
+              "the first key overlays nx, clear of the two pointers");
+// (the fields a ray-sourced job still reads -- seed_mix, total, npix, s_begin, max_depth, div_npix, L -- are
+// none of cam, nx, row_begin, row_step)
+__device__ __forceinline__ const rtw_query_ray* job_rays(const job_t& J) {
+    const rtw_query_ray* rays;
+    __builtin_memcpy(&rays, &J.cam, sizeof rays);
+    return rays;
+}
+__device__ __forceinline__ const uint32_t* job_ray_rng(const job_t& J) { return job_active_list(J); }
+__device__ __forceinline__ uint32_t job_first_key(const job_t& J) { return (uint32_t)J.nx; }
+
+// The start of sample q of a ray-sourced job: q = sample * n_rays + ray, the
+// sample-major order k_reduce sums.  The lane loads its 64-byte record as
+// k_query does (16-byte loads with per-lane addresses, a wave's together whole
+// lines; vector loads, where the refill happens, so nothing of the record is
+// loop-carried beyond the fresh path itself); t_max is not read, and with
+// TIME false (F_STATIC rows keep no time per path) neither is the time: the
+// record's last 16 bytes are then not loaded.  The stream is the caller's
+// state of the ray, or path_seed of (first_key + ray, sample); nothing draws
+// from it before color().
+template <bool TIME = true>
+__device__ __forceinline__ ray ray_sample(const job_t& J, uint32_t q, uint32_t& rng) {
+    const uint32_t sl = udiv_fast(q, J.div_npix);
+    const uint32_t k = q - sl * J.npix;
+    const double2* in = reinterpret_cast<const double2*>(job_rays(J) + k);
+    const double2 a = in[0], b = in[1], c = in[2];
+    ray r;
+    r.o = d3{a.x, a.y, b.x}, r.d = d3{b.y, c.x, c.y}, r.t = 0.0;
+    if constexpr (TIME) r.t = in[3].x;
+    const uint32_t* states = job_ray_rng(J);
+    rng = states ? states[k] : path_seed(J.seed_mix, job_first_key(J) + k, (uint32_t)(J.s_begin + (int)sl));
+    return r;
+}
+// A fresh path of a persistent kernel: the camera's sample, or with F_RAYS the caller's ray.
+template <int F, bool JPIN>
+__device__ __forceinline__ ray fresh_sample(const job_t& J, uint32_t q, uint32_t& rng) {
+    if constexpr ((F & F_RAYS) != 0)
+        return ray_sample<(F & F_STATIC) == 0>(J, q, rng);
+    else
+        return camera_sample<JPIN, (F & F_ACTIVE) != 0>(J, q, rng);
+}
+
+// RAYS: of a ray-sourced job (ACTIVE does not apply)
+template <bool ACTIVE = false, bool RAYS = false>
 __device__ __forceinline__ void raygen(const job_t& J, const fresh_t& F, uint32_t k, uint32_t q) {
     uint32_t rng;
-    const ray r = camera_sample<true, ACTIVE>(J, q, rng);
+    const ray r = RAYS ? ray_sample<true>(J, q, rng) : camera_sample<true, ACTIVE>(J, q, rng);
     F.ox[k] = r.o.x, F.oy[k] = r.o.y, F.oz[k] = r.o.z;
     F.dx[k] = r.d.x, F.dy[k] = r.d.y, F.dz[k] = r.d.z;
     F.tm[k] = r.t;
@@ -939,7 +999,7 @@ void k_persist(persist_args) {
                     if (left) open = false;
                     if (got) {  // (lanes >= NB get no id)
                         uint32_t rng;
-                        const ray r = camera_sample<false, (F & F_ACTIVE) != 0>(J, q, rng);
+                        const ray r = fresh_sample<F, false>(J, q, rng);
                         if constexpr (!PIN) B.ox[ln] = r.o.x, B.oy[ln] = r.o.y, B.oz[ln] = r.o.z;
                         B.dx[ln] = r.d.x, B.dy[ln] = r.d.y, B.dz[ln] = r.d.z;
                         B.tm[ln] = r.t;
@@ -1252,7 +1312,7 @@ void k_persist_sort(persist_args) {
                 }
                 if (left) open = false;
                 if (got) {
-                    const ray r = camera_sample<true, (F & F_ACTIVE) != 0>(J, q, x.rng);
+                    const ray r = fresh_sample<F, true>(J, q, x.rng);
                     const uint32_t me = threadIdx.x;
                     const uint32_t home = X.home[me];
                     X.put_ray(me, r);
@@ -1611,7 +1671,7 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* s_wave, uin
 // measured 52 us vs 5 us per launch for 13 scattered arrays vs 3.)
 constexpr uint32_t kRegenSlots = 1024;
 
-template <bool ACTIVE>
+template <bool ACTIVE, bool RAYS = false>
 __device__ __forceinline__ void regen_block(const job_t& J, const paths_t& P, const fresh_t& FR, ctrs_t* C) {
     __shared__ uint32_t s_wave[kWaves];
     __shared__ uint32_t s_list[kRegenSlots];
@@ -1665,7 +1725,7 @@ __device__ __forceinline__ void regen_block(const job_t& J, const paths_t& P, co
         for (int a = 0; a < kQShards; ++a) {
             if (k < s_got[a]) {
                 const int sh = (own + a) % kQShards;
-                raygen<ACTIVE>(J, FR, lo + e, (uint32_t)shard_sample(sh, s_first[a] + k));
+                raygen<ACTIVE, RAYS>(J, FR, lo + e, (uint32_t)shard_sample(sh, s_first[a] + k));
                 P.depth[s_list[e]] = kFresh | (lo + e);
                 break;
             }
@@ -1682,6 +1742,22 @@ __global__ __launch_bounds__(kBlock) void k_regen(job_t J, paths_t P, fresh_t FR
 __global__ __launch_bounds__(kBlock) void k_regen_active(job_t J, paths_t P, fresh_t FR, ctrs_t* C) {
     regen_block<true>(J, P, FR, C);
 }
+#if !RTW_STRICT_RADIANCE
+// ... of a radiance query (rtw_radiance.h): fresh paths from the caller's ray
+// records (ray_sample), for every feature and material set as k_regen_active
+__global__ __launch_bounds__(kBlock) void k_regen_rays(job_t J, paths_t P, fresh_t FR, ctrs_t* C) {
+    regen_block<false, true>(J, P, FR, C);
+}
+// Rays whose time the BVH's boxes do not cover, counted before anything is
+// traced (a scene with a BVH and moving spheres: rtw_query.h's rule).
+__global__ __launch_bounds__(kBlock) void k_check_ray_times(const rtw_query_ray* __restrict__ rays, uint32_t n,
+                                                            double sh0, double sh1, uint32_t* bad) {
+    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < n; k += gridDim.x * kBlock) {
+        const double t = rays[k].time;
+        if (!(t >= sh0 && t <= sh1)) atomicAdd(bad, 1u);
+    }
+}
+#endif
 
 // Tail-phase stream compaction of live slots (depth != 0) from A into B
 // (fresh markers move with their slot; staging is not rewritten in the tail).
@@ -2592,6 +2668,20 @@ template <size_t... I>
 std::array<const void*, sizeof...(I)> fast_sort_active_rows(std::index_sequence<I...>) {
     return {reinterpret_cast<const void*>(&k_fast_sort<kFastSortActiveList[I].id.f, kFastSortActiveList[I].id.l>)...};
 }
+// ... and the rows of caller-supplied rays (kPersistRaysList), likewise
+template <size_t I>
+const void* persist_rays_fn() {
+    constexpr active_inst a = kPersistRaysList[I];
+    if constexpr (a.form == kform::persist_sort)
+        return reinterpret_cast<const void*>(&k_persist_sort<a.id.f, a.id.m, a.id.l>);
+    else
+        return reinterpret_cast<const void*>(&k_persist<a.id.f, a.id.m, a.id.l, a.form == kform::persist_lst>);
+}
+template <size_t... I>
+std::array<const void*, sizeof...(I)> persist_rays_rows(std::index_sequence<I...>) {
+    return {persist_rays_fn<I>()...};
+}
+const auto kPersistRaysRows = persist_rays_rows(std::make_index_sequence<kPersistRaysList.size()>{});
 const auto kPersistActiveRows = persist_active_rows(std::make_index_sequence<kPersistActiveList.size()>{});
 const auto kFastActiveRows = fast_active_rows(std::make_index_sequence<kFastActiveList.size()>{});
 const auto kFastSortActiveRows = fast_sort_active_rows(std::make_index_sequence<kFastSortActiveList.size()>{});
@@ -2685,6 +2775,31 @@ int plan_render(const handle_t* h, bool pin, bool fast, plan_t* out, bool active
         if (id.l) p.packet = node_packet(p.fn, rtwf::fast_block(id.f), 0, h->F32.n_nodes);
     } else if (form == kform::fast_sort) {
         p.fn = act ? kFastSortActiveRows[at] : kFastSortRows[at];
+    }
+    *out = p;
+    return RTW_OK;
+}
+
+// A radiance query's kernel (rtw_radiance.h, select_rays): a row of
+// kPersistRaysList, or a wavefront form, which wavefront_pass refills with
+// k_regen_rays.
+int plan_rays(const handle_t* h, plan_t* out) {
+    select_in s = scene_facts(h, false);
+    s.env = read_env();
+    plan_t p{select_rays(s)};
+    const kform form = p.c.form;
+    const inst& id = p.c.id;
+    if (form == kform::split) {
+        const split_rows r = split_resolve(id);
+        p.fn = kIntersectRows[index_of(kIntersectList, r.intersect)];
+        p.fn_shade = kShadeRows[index_of(kShadeList, r.shade)];
+        p.shm = r.shade.l ? h->facts.shade_bytes : 0;
+    } else {
+        p.shm = id.l ? h->facts.shade_bytes : 0;
+        const int at = form == kform::segment ? index_of(kSegmentList, id) : index_of(kPersistRaysList, active_inst{id, form});
+        if (at < 0) return rtw_fail(RTW_ERR_HIP, "no such instantiation: " + p.c.name);
+        p.fn = form == kform::segment ? kSegmentRows[at] : kPersistRaysRows[at];
+        if (form == kform::persist_lst) p.packet = node_packet(p.fn, kPBlock, p.shm, h->S.n_nodes);
     }
     *out = p;
     return RTW_OK;
@@ -2994,6 +3109,10 @@ int wavefront_pass(handle_t* h, const plan_t& plan, const job_t& J, const call_p
     int rc;
     // the refill: camera rays of the image's rows, or of the call's pixel list
     const auto regen = [&] {
+#if !RTW_STRICT_RADIANCE
+        if (plan.c.rays) hipLaunchKernelGGL(k_regen_rays, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
+        else
+#endif
         if (plan.c.active) hipLaunchKernelGGL(k_regen_active, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
         else hipLaunchKernelGGL(k_regen, dim3(regen_grid), dim3(kBlock), 0, st, J, W.A, W.FR, C);
     };
@@ -3087,6 +3206,14 @@ job_t make_job(const handle_t* h, const call_plan& P, const rtw_render_params& R
 // ... of an active call: the device list where the rows were (job_active_list)
 void set_job_active_list(job_t& J, const uint32_t* list_dev) {
     std::memcpy(&J.row_begin, &list_dev, sizeof list_dev);
+}
+// ... of a radiance query: the ray records over cam, the caller's stream
+// states (or null) where the rows were, the first key over nx (job_rays,
+// job_ray_rng, job_first_key)
+void set_job_rays(job_t& J, const rtw_query_ray* rays_dev, const uint32_t* rng_dev, uint32_t first_key) {
+    std::memcpy(&J.cam, &rays_dev, sizeof rays_dev);
+    std::memcpy(&J.row_begin, &rng_dev, sizeof rng_dev);
+    std::memcpy(&J.nx, &first_key, sizeof first_key);
 }
 void set_pass(job_t& J, const call_pass& p) {
     J.total = p.total;
@@ -4133,4 +4260,144 @@ extern "C" int rtw_camera_rays(void* handle, const rtw_camera_desc* camera, cons
     HIPCHK(hipStreamSynchronize(st));
     return RTW_OK;
 #endif
+}
+
+// ======================================================================
+// rtw_radiance.h
+// ======================================================================
+#if !RTW_STRICT_RADIANCE
+namespace {
+// The trace of a checked call.  Per chunk (radiance.h): the rays (and states,
+// and sums) on the device, the shutter check where the scene needs it, the
+// chunk's passes through the plan's kernel exactly as render_accumulate runs a
+// render's, k_reduce per pass into the chunk's zeroed sums, and k_add into the
+// caller's.
+int radiance_trace(handle_t* h, const rtw_query_ray* rays, uint64_t n, const uint32_t* rng,
+                   const rtw_radiance_params& prm, double* sum_rgb, rtw_stats* stats) {
+    const char* const what = "rtw_trace_radiance";
+    const radiance_plan P = rtw_radiance_plan(n, prm, rng != nullptr, pass_budget_samples());
+    stats->samples = P.samples;
+    if (n == 0) return RTW_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (prm.on_device)  // (before the max_depth == 0 no-op: a foreign pointer is refused whatever the depth)
+        if (int rc = check_handle_ptrs(h, what, {rays, rng, sum_rgb})) return rc;
+    if (P.noop) return RTW_OK;
+    plan_t plan;
+    if (int rc = plan_rays(h, &plan)) return rc;
+    const bool persistent = plan.c.persistent();
+    if (int rc = h->q_rays.ensure(P.bytes_rays)) return rc;
+    if (int rc = h->q_out.ensure(P.bytes_sums)) return rc;
+    if (int rc = h->q_rng.ensure(P.bytes_rng)) return rc;
+    hipStream_t st = h->stream;
+    uint32_t* bad = nullptr;
+    if (h->facts.bvh_motion) {
+        if (int rc = h->q_bad.ensure(16)) return rc;
+        bad = static_cast<uint32_t*>(h->q_bad.p);
+    }
+    ctrs_t* C = static_cast<ctrs_t*>(h->ctrs.p);
+    HIPCHK(hipMemsetAsync(C, 0, sizeof(ctrs_t), st));
+    call_events E(h, 0);
+    hipEvent_t ev_begin = event_at(h, E.ev++), ev_end = event_at(h, E.ev++);
+    if (!ev_begin || !ev_end) return rtw_fail(RTW_ERR_HIP, "hipEventCreate failed");
+    HIPCHK(hipEventRecord(ev_begin, st));
+    const fast_args FA{};
+    for (uint64_t c = 0; c < P.n_chunks; ++c) {
+        radiance_chunk ch;
+        if (int rc = rtw_radiance_chunk(P, c, &ch)) return rc;
+        const call_plan& CP = ch.call;
+        if (int rc = ensure_buffers(h, CP.bytes, false)) return rc;
+        // the chunk's buffers on the device: the caller's, or the staged copies
+        const rtw_query_ray* r_dev = rays + ch.first;
+        const uint32_t* g_dev = rng ? rng + ch.first : nullptr;
+        double* s_dev = sum_rgb + 3 * ch.first;
+        if (P.staged) {
+            r_dev = static_cast<const rtw_query_ray*>(h->q_rays.p);
+            s_dev = static_cast<double*>(h->q_out.p);
+            HIPCHK(hipMemcpyAsync(h->q_rays.p, rays + ch.first, ch.count * sizeof(rtw_query_ray), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(s_dev, sum_rgb + 3 * ch.first, ch.count * 24, hipMemcpyHostToDevice, st));
+            if (rng) {
+                g_dev = static_cast<const uint32_t*>(h->q_rng.p);
+                HIPCHK(hipMemcpyAsync(h->q_rng.p, rng + ch.first, ch.count * 4, hipMemcpyHostToDevice, st));
+            }
+        }
+        if (bad) {  // before the chunk is traced: a time the boxes do not cover could walk anywhere
+            uint32_t n_bad = 0;
+            HIPCHK(hipMemsetAsync(bad, 0, 4, st));
+            hipLaunchKernelGGL(k_check_ray_times, dim3(reduce_grid(ch.count)), dim3(kBlock), 0, st, r_dev,
+                               (uint32_t)ch.count, h->facts.shutter0, h->facts.shutter1, bad);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&n_bad, bad, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (n_bad)
+                return rtw_fail(RTW_ERR_INVALID, std::string(what) + ": " + std::to_string(n_bad) +
+                                                     " rays have a time outside the shutter the scene's BVH was built "
+                                                     "for (moving spheres)");
+        }
+        wave_pool W{rtw_carve_paths<paths_t>(h->pool[0].p, CP.pool), rtw_carve_paths<paths_t>(h->pool[1].p, CP.pool),
+                    rtw_carve_fresh<fresh_t>(h->fresh.p, CP.pool), static_cast<double*>(h->hits.p),
+                    reinterpret_cast<int32_t*>(static_cast<char*>(h->hits.p) + CP.hits_id_off), CP.pool};
+        double* run = static_cast<double*>(h->run.p);
+        HIPCHK(hipMemsetAsync(run, 0, CP.bytes.run, st));
+        job_t J = make_job(h, CP, ch.R);
+        set_job_rays(J, r_dev, g_dev, ch.first_key);
+        for (uint64_t done = 0; done < (uint64_t)CP.spp_count; done += CP.pass_spp) {
+            const call_pass pass = rtw_plan_pass(CP, ch.R, done);
+            set_pass(J, pass);
+            if (persistent) {
+                hipLaunchKernelGGL(k_fill, dim3(1), dim3(kBlock), 0, st, W.A, C, 0u);  // reset the queue
+                launch_persistent(plan, h, st, J, C, FA);
+                HIPCHK(hipGetLastError());
+                stats->launches_intersect++;
+                stats->iterations++;
+            } else if (int rc = wavefront_pass(h, plan, J, pass, W, E, *stats)) {
+                return rc;
+            }
+            launch_reduce(st, false, J.L, CP.npix, pass.spp_pass, run, nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        const size_t n3 = (size_t)ch.count * 3;
+        hipLaunchKernelGGL(k_add, dim3(grid_for(n3)), dim3(kBlock), 0, st, s_dev, run, n3);
+        HIPCHK(hipGetLastError());
+        if (P.staged) {
+            HIPCHK(hipMemcpyAsync(sum_rgb + 3 * ch.first, s_dev, ch.count * 24, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));  // (the staging buffers are the next chunk's)
+        }
+    }
+    HIPCHK(hipMemcpyAsync(&h->host_ctrs[63], C, sizeof(ctrs_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(ev_end, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end));
+    stats->ms_total = ms;
+    for (int k = 0; k < 8; ++k) stats->segments += h->host_ctrs[63].segments[k].v;
+    stats->bytes_intersect = 68.0 * (double)stats->segments;
+    return RTW_OK;
+}
+}  // namespace
+#endif
+
+extern "C" int rtw_trace_radiance(void* handle, const rtw_query_ray* rays, uint64_t n, const uint32_t* rng,
+                                  const rtw_radiance_params* prm, double* sum_rgb, rtw_stats* out_stats) {
+    handle_t* h = static_cast<handle_t*>(handle);
+    if (int rc = rtw_radiance_check_args(h, rays, n, rng, prm, sum_rgb, RTW_STRICT_RADIANCE != 0)) return rc;
+    rtw_stats stats;
+    std::memset(&stats, 0, sizeof stats);
+    int rc = RTW_OK;
+#if !RTW_STRICT_RADIANCE
+    rc = radiance_trace(h, rays, n, rng, *prm, sum_rgb, &stats);
+#endif
+    if (!rc && out_stats) *out_stats = stats;
+    return rc;
+}
+
+extern "C" int rtw_scene_query_radiance(void* handle, char name[128]) {
+    const handle_t* h = static_cast<const handle_t*>(handle);
+    if (!h || !name) return rtw_fail(RTW_ERR_INVALID, "rtw_scene_query_radiance: null argument");
+    if (RTW_STRICT_RADIANCE)
+        return rtw_fail(RTW_ERR_UNSUPPORTED, "the strict-radiance build has no query kernels (rtw_trace_radiance)");
+    HIPCHK(hipSetDevice(h->device));  // occupancy queries of the plan
+    plan_t p;
+    if (int rc = plan_rays(h, &p)) return rc;
+    std::snprintf(name, 128, "%s", p.c.name.c_str());
+    return RTW_OK;
 }

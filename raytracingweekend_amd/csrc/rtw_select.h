@@ -35,7 +35,11 @@ enum : int { F_MEDIA = 1, F_WBVH = 2, F_GBVH = 4, F_YSPH = 8, F_STATIC = 16, F_L
              // pixel is read from the active list (rtw_kernels.hip sample_coords).
              // Only the instantiations of the active lists below carry the bit;
              // it is free in the FF_* range of the fp32 kernels too.
-             F_ACTIVE = 512 };
+             F_ACTIVE = 512,
+             // the paths start from rays the caller supplies (rtw_radiance.h): a fresh
+             // path's ray and stream come from the job's ray records, not the camera
+             // (rtw_kernels.hip ray_sample).  Only kPersistRaysList's rows carry the bit.
+             F_RAYS = 1024 };
 // fp32 kernels for scenes without a noise texture (F bit, fast kernels only):
 // the marble texture compiled out of shading (rtw_fast.h texture_value)
 constexpr int FF_NONOISE = 1 << 12;
@@ -236,6 +240,21 @@ constexpr std::array kFastSortActiveList{active_inst{{FF_NONOISE | F_ACTIVE, -1,
 constexpr std::array<active_inst, 0> kPersistActiveList{}, kFastActiveList{}, kFastSortActiveList{};
 #endif
 
+// Kernels whose paths start from caller-supplied rays (F_RAYS, rtw_radiance.h):
+// as the active lists, one row per built-in scene in the form it runs by
+// default.  No row carries F_PIN: the pinhole batches and the camera-origin
+// shortcut assume that every path starts at the camera.  Every other scene
+// takes the wavefront forms, refilled by k_regen_rays.
+#if !defined(RTW_SUBSET) && !defined(RTW_SUBSET_FAST) && !(defined(RTW_STRICT_RADIANCE) && RTW_STRICT_RADIANCE)
+constexpr std::array kPersistRaysList{
+    active_inst{{F_STATIC | F_LIGHTS | F_BLACK | F_RAYS, SF_DIEL, true}, kform::persist_sort},          // Cornell
+    active_inst{{F_YSPH | F_NOLIGHTS | F_RAYS, SF_METAL | SF_DIEL, false}, kform::persist_sort},        // random_balls
+    active_inst{{F_WBVH | F_NOLIGHTS | F_RAYS, SF_METAL | SF_DIEL, false}, kform::persist_lst},         // ... with a BVH
+    active_inst{{F_MEDIA | F_GBVH | F_LIGHTS | F_BLACK | F_RAYS, SF_NOCHECKER, false}, kform::persist_lst}};  // Book 2 with BVHs
+#else  // (those builds have no radiance queries: the strict build refuses them)
+constexpr std::array<active_inst, 0> kPersistRaysList{};
+#endif
+
 struct select_env {
     bool wavefront = false;  // RTW_MODE=wavefront: no persistent kernel (fp64)
     bool split = false;      // RTW_SPLIT=1: k_intersect + k_shade, not k_segment
@@ -262,6 +281,7 @@ struct kernel_choice {
     inst id;  // the template arguments; split: {features, shade set, LDS shading}, the rows by split_resolve
     std::string name;
     bool active = false;  // select_active's: a row of the active lists, or a wavefront form refilled by k_regen_active
+    bool rays = false;    // select_rays': a row of kPersistRaysList, or a wavefront form refilled by k_regen_rays
     bool persistent() const { return form != kform::segment && form != kform::split; }
 };
 
@@ -393,6 +413,30 @@ inline kernel_choice select_active(const select_in& s_in, bool fp32) {
     kernel_choice w = select_fp64(s);
     w.name = "k_regen_active + " + w.name;
     w.active = true;
+    return w;
+}
+
+// A radiance query (rtw_radiance.h, fp64 only): the paths start from the
+// caller's rays.  The kernel a render of the scene with a camera that is no
+// pinhole runs (F_PIN never applies: the rays start anywhere), with F_RAYS,
+// where kPersistRaysList holds it in that form; else the wavefront forms as
+// select_fp64 picks them under RTW_MODE=wavefront, named with the k_regen_rays
+// that refills them.  RTW_MODE, RTW_SORT and RTW_SPLIT act as for renders.
+inline kernel_choice select_rays(const select_in& s_in) {
+    select_in s = s_in;
+    s.active = false;
+    s.pin = false;
+    const kernel_choice c = select_fp64(s);
+    const active_inst want{{c.id.f | F_RAYS, c.id.m, c.id.l}, c.form};
+    if (!s.strict && c.persistent() && index_of(kPersistRaysList, want) >= 0) {
+        const bool sort = c.form == kform::persist_sort;
+        return {c.form, want.id, kname(sort ? "k_persist_sort" : "k_persist", want.id.f, want.id.m, want.id.l,
+                                       sort ? -1 : c.form == kform::persist_lst ? 1 : 0), false, true};
+    }
+    s.env.wavefront = true;
+    kernel_choice w = select_fp64(s);
+    w.name = "k_regen_rays + " + w.name;
+    w.rays = true;
     return w;
 }
 

@@ -11,6 +11,14 @@
 //                            [--adaptive-window R]]
 //              [--denoise [--denoise-iterations 5]]
 //   rtw_render --scene S [--bvh] --rays rays.bin --hits hits.bin [--occluded] [--rng rng.bin]
+//   rtw_render --scene S [--bvh] --rays rays.bin --radiance sums.bin --spp N [--depth D] [--seed S] [--rng rng.bin]
+//
+// --rays rays.bin --radiance sums.bin path-traces the caller's rays
+// (rtw_radiance.h): samples [0, --spp) of every ray, ray k keyed k, --depth as
+// color()'s depth; sums.bin receives raw doubles, 3 per ray, each ray's sum of
+// its samples.  With --rng rng.bin (one uint32 state per ray, --spp 1) ray k's
+// sample starts from that state; the file is not rewritten.  Not with --hits,
+// --occluded or --out.  Prints one "Radiance:" line.  One GPU.
 //
 // --rays rays.bin --hits hits.bin traces the caller's rays instead of rendering
 // (rtw_query.h): rays.bin holds raw rtw_query_ray records, hits.bin receives
@@ -65,45 +73,83 @@
 #include "rtw_denoise.h"
 #include "rtw_noise.h"
 #include "rtw_query.h"
+#include "rtw_radiance.h"
 
 namespace {
-// --rays: trace the file's rays on `handle`, write the hits (or flags)
-int run_query(void* handle, const std::string& rays_path, const std::string& hits_path, const std::string& rng_path,
-              bool occluded) {
-    auto slurp = [](const std::string& path, std::vector<char>& out) {
-        FILE* f = std::fopen(path.c_str(), "rb");
-        if (!f) return false;
-        std::fseek(f, 0, SEEK_END);
-        const long n = std::ftell(f);
-        std::fseek(f, 0, SEEK_SET);
-        out.resize(n > 0 ? (size_t)n : 0);
-        const bool ok = out.empty() || std::fread(out.data(), 1, out.size(), f) == out.size();
-        std::fclose(f);
-        return ok;
-    };
-    auto spill = [](const std::string& path, const void* data, size_t bytes) {
-        FILE* f = std::fopen(path.c_str(), "wb");
-        if (!f) return false;
-        const bool ok = bytes == 0 || std::fwrite(data, 1, bytes, f) == bytes;
-        return std::fclose(f) == 0 && ok;
-    };
+bool slurp(const std::string& path, std::vector<char>& out) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return false;
+    std::fseek(f, 0, SEEK_END);
+    const long n = std::ftell(f);
+    std::fseek(f, 0, SEEK_SET);
+    out.resize(n > 0 ? (size_t)n : 0);
+    const bool ok = out.empty() || std::fread(out.data(), 1, out.size(), f) == out.size();
+    std::fclose(f);
+    return ok;
+}
+bool spill(const std::string& path, const void* data, size_t bytes) {
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = bytes == 0 || std::fwrite(data, 1, bytes, f) == bytes;
+    return std::fclose(f) == 0 && ok;
+}
+// the rays of --rays and the states of --rng (empty path: none)
+bool load_rays(const std::string& rays_path, const std::string& rng_path, std::vector<rtw_query_ray>& rays,
+               std::vector<uint32_t>& rng) {
     std::vector<char> raw, raw_rng;
     if (!slurp(rays_path, raw) || raw.size() % sizeof(rtw_query_ray)) {
         std::fprintf(stderr, "--rays %s: not a file of %zu-byte ray records\n", rays_path.c_str(), sizeof(rtw_query_ray));
-        return 1;
+        return false;
     }
     const uint64_t n = raw.size() / sizeof(rtw_query_ray);
-    std::vector<rtw_query_ray> rays(n);
+    rays.resize(n);
     if (n) std::memcpy(rays.data(), raw.data(), raw.size());
-    std::vector<uint32_t> rng;
     if (!rng_path.empty()) {
         if (!slurp(rng_path, raw_rng) || raw_rng.size() != n * 4) {
             std::fprintf(stderr, "--rng %s: expected one uint32 state per ray\n", rng_path.c_str());
-            return 1;
+            return false;
         }
         rng.resize(n);
         if (n) std::memcpy(rng.data(), raw_rng.data(), raw_rng.size());
     }
+    return true;
+}
+
+// --rays --radiance: path-trace the file's rays on `handle`, write the per-ray sums
+int run_radiance(void* handle, const std::string& rays_path, const std::string& sums_path, const std::string& rng_path,
+                 int spp, int depth, unsigned long long seed) {
+    std::vector<rtw_query_ray> rays;
+    std::vector<uint32_t> rng;
+    if (!load_rays(rays_path, rng_path, rays, rng)) return 1;
+    const uint64_t n = rays.size();
+    rtw_radiance_params rp;
+    std::memset(&rp, 0, sizeof rp);
+    rp.max_depth = depth, rp.spp_count = spp, rp.seed = seed, rp.precision = RTW_PRECISION_FP64;
+    rtw_stats st;
+    std::memset(&st, 0, sizeof st);
+    char kernel[128] = "";
+    std::vector<double> sums(n * 3, 0.0);
+    if (rtw_scene_query_radiance(handle, kernel) != RTW_OK ||
+        rtw_trace_radiance(handle, rays.data(), n, rng_path.empty() ? nullptr : rng.data(), &rp, sums.data(), &st) != RTW_OK) {
+        std::fprintf(stderr, "radiance: %s\n", rtw_last_error());
+        return 1;
+    }
+    if (!spill(sums_path, sums.data(), sums.size() * sizeof(double))) {
+        std::fprintf(stderr, "cannot write %s\n", sums_path.c_str());
+        return 1;
+    }
+    std::printf("Radiance: %s  rays %llu  samples %llu  segments %llu  %.3f ms\n", kernel, (unsigned long long)n,
+                (unsigned long long)st.samples, (unsigned long long)st.segments, st.ms_total);
+    return 0;
+}
+
+// --rays: trace the file's rays on `handle`, write the hits (or flags)
+int run_query(void* handle, const std::string& rays_path, const std::string& hits_path, const std::string& rng_path,
+              bool occluded) {
+    std::vector<rtw_query_ray> rays;
+    std::vector<uint32_t> rng;
+    if (!load_rays(rays_path, rng_path, rays, rng)) return 1;
+    const uint64_t n = rays.size();
     rtw_query_params qp;
     std::memset(&qp, 0, sizeof qp);
     qp.precision = RTW_PRECISION_FP64;
@@ -147,8 +193,8 @@ int main(int argc, char** argv) {
     bool window_given = false;
     bool denoise = false;
     int denoise_iterations = -1;  // (not given: the library's default)
-    std::string rays_path, hits_path, rng_path;
-    bool occluded = false;
+    std::string rays_path, hits_path, rng_path, radiance_path;
+    bool occluded = false, out_given = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -166,7 +212,7 @@ int main(int argc, char** argv) {
         else if (a == "--seed") seed = std::strtoull(next(), nullptr, 10);
         else if (a == "--device") device = std::atoi(next());
         else if (a == "--gpus") gpus = std::atoi(next());
-        else if (a == "--out") out = next();
+        else if (a == "--out") out = next(), out_given = true;
         else if (a == "--bvh") bvh = 1;
         else if (a == "--image") image = next();
         else if (a == "--noise") noise = true;
@@ -179,6 +225,7 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--rays") rays_path = next();
         else if (a == "--hits") hits_path = next();
+        else if (a == "--radiance") radiance_path = next();
         else if (a == "--rng") rng_path = next();
         else if (a == "--occluded") occluded = true;
         else if (a == "--denoise-iterations") denoise_iterations = std::atoi(next()), denoise = true;
@@ -227,7 +274,14 @@ int main(int argc, char** argv) {
         return 2;
     }
 
-    if (rays_path.empty() != hits_path.empty() || (rays_path.empty() && (occluded || !rng_path.empty())) ||
+    if (!radiance_path.empty()) {
+        if (rays_path.empty() || !hits_path.empty() || occluded || out_given || gpus != 1 || noise || adaptive || denoise ||
+            precision != RTW_PRECISION_FP64 || spp < 1 || depth < 0) {
+            std::fprintf(stderr, "--rays FILE --radiance FILE --spp N [--depth D] [--rng FILE] go together, on one GPU, in "
+                                 "fp64, without --hits, --occluded, --out or a render's options\n");
+            return 2;
+        }
+    } else if (rays_path.empty() != hits_path.empty() || (rays_path.empty() && (occluded || !rng_path.empty())) ||
         (!rays_path.empty() && (gpus != 1 || noise || adaptive || denoise))) {
         std::fprintf(stderr, "--rays FILE --hits FILE [--occluded] [--rng FILE] go together, on one GPU, without a render's "
                              "options\n");
@@ -269,6 +323,12 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "upload: %s\n", rtw_last_error());
             return 1;
         }
+    if (!radiance_path.empty()) {
+        const int rc = run_radiance(h[0], rays_path, radiance_path, rng_path, spp, depth, seed);
+        rtw_scene_free(h[0]);
+        rtw_scene_desc_free(desc);
+        return rc;
+    }
     if (!rays_path.empty()) {
         const int rc = run_query(h[0], rays_path, hits_path, rng_path, occluded);
         rtw_scene_free(h[0]);

@@ -478,6 +478,59 @@ class DeviceScene:
         check(lib().rtw_scene_query_trace(self.handle, a, b), "rtw_scene_query_trace")
         return a.value.decode(), b.value.decode()
 
+    # ---- radiance queries (include/rtw_radiance.h) ------------------------------
+    def trace_radiance(self, rays, spp: int, max_depth: int, *, seed: int = 0, spp_begin: int = 0,
+                       first_key: int = 0, rng=None, out=None, wavefront_paths: int = 0,
+                       precision: str = "fp64"):
+        """rtw_trace_radiance of the caller's rays ((n, 8) float64 rows (o, d,
+        time, t_max), numpy or a CUDA tensor of this device as trace_rays
+        takes them): path-traces samples [spp_begin, spp_begin + spp) of every
+        ray, ray k keyed first_key + k, and ADDS each ray's sum to row k of
+        `out` ((n, 3) float64 of the rays' kind; None: fresh zeros).  `rng`
+        (n minstd states of the rays' kind, read only): ray k's one sample
+        starts from rng[k] instead (spp must be 1) -- with camera_rays' output
+        these are a render's own paths.  Returns the sums; the call's stats are
+        left in self.last_query_stats."""
+        on_device = not isinstance(rays, np.ndarray)
+        if on_device:
+            import torch
+            if (rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous()
+                    or not rays.is_cuda or rays.device.index != self.device):
+                raise ValueError("rays must be a contiguous (n, 8) float64 tensor on this scene's GPU")
+            n = rays.shape[0]
+            if out is None:
+                out = torch.zeros((n, 3), dtype=torch.float64, device=rays.device)
+            elif (isinstance(out, np.ndarray) or out.dtype != torch.float64 or tuple(out.shape) != (n, 3)
+                  or not out.is_contiguous() or not out.is_cuda or out.device.index != self.device):
+                raise ValueError("out must be a contiguous (n, 3) float64 tensor on this scene's GPU")
+            torch.cuda.synchronize(rays.device)
+            p_rays, p_out = C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr())
+        else:
+            if rays.dtype != np.float64 or rays.ndim != 2 or rays.shape[1] != 8 or not rays.flags["C_CONTIGUOUS"]:
+                raise ValueError("rays must be a contiguous (n, 8) float64 array")
+            n = rays.shape[0]
+            if out is None:
+                out = np.zeros((n, 3), dtype=np.float64)
+            elif (not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.shape != (n, 3)
+                  or not out.flags["C_CONTIGUOUS"]):
+                raise ValueError("out must be a contiguous (n, 3) float64 array")
+            p_rays, p_out = rays.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+        prm = _abi.rtw_radiance_params(max_depth=max_depth, spp_begin=spp_begin, spp_count=spp,
+                                       on_device=int(on_device), seed=seed, first_key=first_key,
+                                       precision=_abi.PRECISIONS[precision], wavefront_paths=wavefront_paths)
+        st = _abi.rtw_stats()
+        check(lib().rtw_trace_radiance(self.handle, p_rays, n, self._rng_ptr(rng, n, on_device), C.byref(prm), p_out,
+                                       C.byref(st)), "rtw_trace_radiance")
+        self.last_query_stats = st.as_dict()
+        return out
+
+    def query_radiance(self) -> str:
+        """rtw_scene_query_radiance: the kernel(s) trace_radiance launches under
+        the current environment."""
+        a = C.create_string_buffer(128)
+        check(lib().rtw_scene_query_radiance(self.handle, a), "rtw_scene_query_radiance")
+        return a.value.decode()
+
     def finalize_device(self, accum, nx: int, ny: int, spp: int, canvas=None):
         """canvas = min(sqrt(accum / spp), 1) on the GPU (torch float64 CUDA
         tensors of nx*ny*3 on this device).  Returns the canvas tensor."""
